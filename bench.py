@@ -9,7 +9,7 @@ the RCCL all-gather of the trajectory records when N > 1.
 Metric (BASELINE.json): MCTS node-expansions/sec (one expansion = one NNetWrapper.predict
 of the reference = one new MCTS.Ps entry), whole job, plus episodes/s.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `python bench.py --gpus N` (N > 1) with no launcher environment starts the N ranks itself
@@ -18,6 +18,12 @@ line; under torch.distributed.run each rank runs main() directly.
 
 Prints ONE JSON line on rank 0.  Data: synthetic (games from seeded streams), random-init
 YachtNNet (kaiming-uniform per YachtNNet._init, seed 0, hidden 256, 6 blocks).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything
+else the benchmark measures, each a run of its own after the timed steps (the Coach legs, the
+config-3 shape, the fp16 predict mode, the Arena and train legs, the CPU baseline) and the
+per-kernel event timing with its rooflines; the --no-* options drop single legs of a --full run.
+--dump-outputs DIR writes the records of the last timed step (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -457,6 +463,39 @@ def coach_leg(model, image, n_envs, max_moves, sims, world, train_steps=60, aren
             "arena_tally_prev_new_draws": [pw, nw, dr]}
 
 
+DUMP_GAMES = 64  # games --dump-outputs keeps: 64 x 48 x 3226 visit counts in float32 are 39.6 MB (limit: 64 MB)
+
+
+def dump_outputs(rec, expansions, path, sample_seed=0):
+    """--dump-outputs: the records a caller of the timed path receives (SelfPlayEngine.records()
+    after the last timed step) as path/<name>.npy, for a fixed, seeded sample of DUMP_GAMES games
+    (`games`, sorted; all of them when there are no more) so that two builds compare output for
+    output.  float64 throughout (the u64 fields as their low / high 32-bit halves, so every bit
+    survives), but the per-move visit counts, dense over the 3226 actions, in float32 (exact:
+    counts <= sims); `expansions` is the whole batch's count of the last step."""
+    import numpy as np
+    E, M = rec["values"].shape
+    pick = np.sort(np.random.default_rng(sample_seed).choice(E, size=min(E, DUMP_GAMES), replace=False))
+
+    def halves(a):  # u64 [..., k] -> f64 [..., 2k]: (low, high) of each word
+        a = np.ascontiguousarray(a)
+        return a.view(np.uint32).reshape(a.shape[:-1] + (2 * a.shape[-1],)).astype(np.float64)
+
+    counts = np.zeros((len(pick), M, A), dtype=np.float32)
+    for r, e in enumerate(pick):
+        for m in range(int(rec["n_moves"][e])):
+            v = rec["visits"][rec["visits_off"][e * M + m]:rec["visits_off"][e * M + m + 1]]
+            counts[r, m, v[:, 0]] = v[:, 1]
+    out = {"games": pick.astype(np.float64), "states": halves(rec["states"][pick]),
+           "info": rec["info"][pick].astype(np.float64), "ctr": halves(rec["ctr"][pick]),
+           "values": rec["values"][pick].astype(np.float64), "final": halves(rec["final"][pick]),
+           "n_moves": rec["n_moves"][pick].astype(np.float64), "visit_counts": counts,
+           "expansions": np.array([expansions], dtype=np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -587,6 +626,12 @@ def main():
     ap.add_argument("--envs", type=int, default=4096, help="games per GPU")
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg after the timed steps and time the kernels with events "
+                         "inside them (off: set up, warm up, time the steps, print the line); the --no-* "
+                         "options below drop single parts of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel event timing")
     ap.add_argument("--profile-stride", type=int, default=20,
@@ -613,6 +658,11 @@ def main():
     ap.add_argument("--spawn-timeout", type=float, default=3000.0,
                     help="--gpus N > 1 without a launcher's WORLD_SIZE: seconds the self-spawned ranks may take")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if not args.full:  # a plain run: the timed steps and the line, nothing else
+        args.no_profile = args.no_coach = args.no_shape = args.no_f16 = args.no_arena = args.no_train = True
+        args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: this process starts the N ranks itself (before touching the GPU) and relays
         # rank 0's line; under torchrun (WORLD_SIZE set) each rank runs the code below
@@ -682,6 +732,8 @@ def main():
     st = eng.stats()
     if st["errors"]:
         raise SystemExit(f"engine error flags {st['errors']}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng.records(), st["expansions"], args.dump_outputs)
 
     tot = torch.tensor([elapsed, float(exps), float(games)], dtype=torch.float64,
                        device="cuda" if world > 1 and dist.get_backend() == "nccl" else "cpu")

@@ -25,7 +25,7 @@ for v in "$@"; do
        ARGS[$n]="" ;;
   esac
 done
-B="python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-arena --no-train --no-coach --no-shape"
+B="python -u bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-arena --no-train --no-coach --no-shape"
 for r in $(seq 1 "$R"); do
   for n in "${names[@]}"; do
     YK_LIB_PATH=${LIB[$n]} timeout -k 10 120 $B ${ARGS[$n]} > gpurun_out/ab_${n}_$r.json 2> gpurun_out/ab_${n}_$r.err || exit $?

@@ -6,6 +6,7 @@ usage: python tools/collect_profiles.py TAG [ENVS SIMS]
       profiles/TAG_forward_traffic.json / TAG_expand_traffic.json (HBM bytes per launch) and
       profiles/TAG_forward_mfma.json (MFMA busy fraction), which bench.py reads for its line
   gpurun_out/dist2_TAG.json            -> profiles/TAG_dist2_gloo_rehearsal.json
+The bench line is also looked for where tools/evidence.sh puts it ($YK_EVIDENCE_DIR, default evidence/).
 """
 import glob
 import json
@@ -19,7 +20,7 @@ envs, sims = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (409
 src, dst = os.path.join(REPO, "gpurun_out"), os.path.join(REPO, "profiles")
 cfg = {"envs": envs, "sims": sims, "hidden": 256, "nblocks": 6}
 cmd = (f"tools/profile_bench.sh {tag}: rocprofv3 --kernel-include-regex 'k_forward|k_expand_backup' --pmc "
-       "FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "
+       "FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline "
        "--no-arena --no-coach --no-shape --no-f16 --no-train --no-profile")
 
 
@@ -30,6 +31,8 @@ def copy(a, b):
 
 
 copy(os.path.join(src, f"bench_{tag}.json"), os.path.join(dst, f"{tag}_bench.json"))
+copy(os.path.join(REPO, os.environ.get("YK_EVIDENCE_DIR", "evidence"), f"bench_{tag}.json"),
+     os.path.join(dst, f"{tag}_bench.json"))
 copy(os.path.join(src, f"dist2_{tag}.json"), os.path.join(dst, f"{tag}_dist2_gloo_rehearsal.json"))
 st = glob.glob(os.path.join(src, f"prof_{tag}", "trace", "**", "*kernel_stats.csv"), recursive=True)
 if st:
@@ -58,8 +61,8 @@ if os.path.exists(summ):
             out = {"kernel": short, "config": cfg, "kernel_src_sha16": s.get("kernel_src_sha16"),
                    "command": f"tools/profile_bench.sh {tag}: rocprofv3 --kernel-include-regex k_forward --pmc "
                               "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -- python3 "
-                              "bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-arena --no-coach --no-shape "
-                              "--no-f16 --no-train --no-profile",
+                              "bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-arena --no-coach "
+                              "--no-shape --no-f16 --no-train --no-profile",
                    "counters_mean_per_launch": {c: v[c + "_mean"] for c in ("SQ_VALU_MFMA_BUSY_CYCLES", "SQ_BUSY_CYCLES",
                                                                           "SQ_WAVE_CYCLES", "GRBM_GUI_ACTIVE")},
                    "busy_frac": v["mfma_busy_frac"],

@@ -4,7 +4,7 @@
 # Each recipe is one or more tools/gpu_steps.sh steps (own time limit; a timeout, abort or fault
 # stops the call).  Variant libraries are prebuilt here into tools/_variants/NAME/ (tools/variant_lib.sh).
 #   tests       pytest -m gpu (every GPU test), then __graft_entry__.smoke()
-#   bench       python bench.py (the default line, every leg)      -> gpurun_out/bench_TAG.json
+#   bench       python bench.py --full (the line with every leg)   -> $YK_EVIDENCE_DIR/bench_TAG.json
 #   prof        tools/profile_bench.sh TAG: rocprofv3 kernel trace + FETCH/WRITE/MFMA passes
 #   ab[:R[:V..]] tools/ab_bench.sh R (default 3) head vs base [vs variants V = NAME=FLAGS]
 #   train       the AMP and the f32 train step times (tools/train_time.py, 512 examples)
@@ -17,19 +17,22 @@
 #   amp         per-wave stamps of the AMP train step (YK_AMP_TIMING build, tools/diag_amp.py)
 #   xlane       tools/_xlane_check: the DPP / permlane exchanges against __shfl_xor
 #   dist2       2 gloo ranks sharing the GPU (tools/dist_rehearsal.sh) -> gpurun_out/dist2_TAG.json
-#   spawn2      the same through bench.py's own launcher (--gpus 2, no torchrun) -> gpurun_out/spawn2_TAG.json
+#   spawn2      the same through bench.py's own launcher (--gpus 2, no torchrun) -> $YK_EVIDENCE_DIR/spawn2_TAG.json
 #   cores       bench.host_cores(): affinity mask, cgroup quota, OMP_NUM_THREADS of the box
+# YK_EVIDENCE_DIR (default evidence/, git-ignored) takes the bench lines of `bench` and `spawn2`.
 # Example: tools/evidence.sh r05a tests bench prof ab:3:contract=-DXP_CONTRACT
 cd "$(dirname "$0")/.." || exit 2
 tag=$1
 shift
 [ -n "$tag" ] || { echo "usage: tools/evidence.sh TAG RECIPE..." >&2; exit 2; }
+ev=${YK_EVIDENCE_DIR:-evidence}
+mkdir -p "$ev"
 steps=()
 for r in "$@"; do
   case "$r" in
     tests) steps+=("gputests:600:python -u -m pytest tests -m gpu -q --timeout 150 --timeout-method thread -rf"
                    'smoke:200:python -u -c "import __graft_entry__ as g; g.smoke()"') ;;
-    bench) steps+=("bench:600:python -u bench.py > gpurun_out/bench_$tag.json") ;;
+    bench) steps+=("bench:600:python -u bench.py --full > $ev/bench_$tag.json") ;;
     prof) steps+=("prof:900:bash tools/profile_bench.sh $tag") ;;
     ab*) IFS=: read -r _ rounds rest <<< "$r"
          steps+=("ab:900:bash tools/ab_bench.sh ${rounds:-3} ${rest//,/ }") ;;
@@ -44,7 +47,7 @@ for r in "$@"; do
     amp) steps+=("amp_ts:120:YK_LIB_PATH=tools/_variants/amp/libyacht_hip.so python -u tools/diag_amp.py") ;;
     xlane) steps+=("xlane:60:tools/_xlane_check") ;;
     dist2) steps+=("dist2:600:bash tools/dist_rehearsal.sh > gpurun_out/dist2_$tag.json") ;;
-    spawn2) steps+=("spawn2:600:python3 -u bench.py --gpus 2 --dist-backend gloo --envs 1024 --sims 25 --steps 1 --warmup 1 --coach-games 1024 --no-steady > gpurun_out/spawn2_$tag.json") ;;
+    spawn2) steps+=("spawn2:600:python3 -u bench.py --gpus 2 --dist-backend gloo --envs 1024 --sims 25 --steps 1 --warmup 1 --coach-games 1024 --no-steady --full > $ev/spawn2_$tag.json") ;;
     cores) steps+=('cores:60:python3 -c "import bench, json; print(json.dumps(bench.host_cores()))"') ;;
     *) echo "unknown recipe $r" >&2; exit 2 ;;
   esac

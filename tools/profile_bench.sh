@@ -10,7 +10,7 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 # the kernel sources measured (bench.py matches its roofline inputs to them)
 python3 -c "import bench; print(bench.kernel_sources_sha16())" > $out/kernel_src_sha16.txt
-args="--steps 1 --warmup 1 --no-cpu-baseline --no-arena --no-coach --no-shape --no-f16 --no-train"
+args="--full --steps 1 --warmup 1 --no-cpu-baseline --no-arena --no-coach --no-shape --no-f16 --no-train"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o bench --output-format csv -- python3 bench.py $args > $out/bench_trace.json
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 400 rocprofv3 --kernel-include-regex 'k_forward|k_expand_backup' --pmc $c -d $out/$c -o $c --output-format csv -- python3 bench.py $args --no-profile > $out/bench_$c.json
