@@ -55,8 +55,10 @@ struct NodeRec {          // 96 bytes
     uint32_t p_off;       // arena offset (entries) of P / slots
     uint32_t nvalid;
     uint32_t Ns;
-    uint32_t pad;
+    uint32_t first_j;     // the node summary: the full UCB scan's pick at Ns = 0 (0x7FFFFFFF: none), so a
+                          // node's first scan reads neither its P nor its slots
 };
+static_assert(sizeof(NodeRec) == 96, "NodeRec: 96 bytes");
 struct Edge {             // 16 bytes
     double Q;
     uint32_t N;
@@ -97,6 +99,7 @@ struct EngDev {
                            //        nvalid, entries of its P order}, {vinfo lo, hi, visited root edges in
                            //        rv (RV_OFF: no P order this move), walk start: the order's entries
                            //        before it are all visited}; one 32-byte read for root_scan
+    int node_summary;      // 1: a node's first UCB scan takes the record's first_j (YK_NODE_SUMMARY=0: full scans)
     int ro_k;              // entries of the root's order k_root_sort keeps (RO_K; YK_ROOT_K for the tests)
     uint32_t* rv;          // [T][RV_CAP] j | slot << 12 of each visited root edge
     uint16_t* ro_j;        // [T][RO_K] the root's top compact indices by descending P (ascending j on ties)
@@ -624,8 +627,8 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
         }
         return;
     }
-    const int t = tree_of(d, e);
-    const int g = d.gen[t];
+    const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
+    const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
     YkS s = ld_state(d.root + e);
     Stream rs{d.seed, env_ids[e], ctr_arr[e]};
     const NodeRec* nodes = d.nodes[g] + (long)t * d.NCAP;
@@ -718,32 +721,40 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
             float best = -INFINITY;
             int bj = 0x7FFFFFFF;
             uint32_t btag = 0;  // the edge tag of the lane's best entry (0: unvisited)
+            // the node summary (an interior node, or a root in full-scan mode): at Ns = 0 no edge is
+            // visited and every term is (c P) sqe0, so the pick is the one the expansion stored.  It
+            // seeds every lane and leaves the scan nothing to read (a second exit path here spills).
+            int Vs = V;  // entries the full scan reads
+            if (d.node_summary && Ns == 0) {
+                bj = (int)nd.first_j;
+                Vs = 0;
+            }
             // software-pipelined scan: iteration it+1's P / slot loads fly while iteration it's
             // visited-edge gathers resolve
             float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f);
             ushort4 s4 = make_ushort4(0, 0, 0, 0);
-            if (lane * 4 < V) {
+            if (lane * 4 < Vs) {
                 p4 = *reinterpret_cast<const float4*>(P + lane * 4);
                 s4 = *reinterpret_cast<const ushort4*>(S + lane * 4);
             }
-            for (int j0 = lane * 4; j0 < V; j0 += 256) {
+            for (int j0 = lane * 4; j0 < Vs; j0 += 256) {
                 const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
                 const uint16_t sv[4] = {s4.x, s4.y, s4.z, s4.w};
                 Edge ev[4];
 #pragma unroll
                 for (int t = 0; t < 4; t++)
-                    if (j0 + t < V && sv[t]) {
+                    if (j0 + t < Vs && sv[t]) {
                         ev[t] = edges[sv[t] - 1];
                         ngl++;
                     }
-                if (j0 + 256 < V) {
+                if (j0 + 256 < Vs) {
                     p4 = *reinterpret_cast<const float4*>(P + j0 + 256);
                     s4 = *reinterpret_cast<const ushort4*>(S + j0 + 256);
                 }
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int j = j0 + t;
-                    if (j < V) {
+                    if (j < Vs) {
                         float u;
                         const float cp = d.c32 * pv[t];
                         if (sv[t]) {
@@ -759,8 +770,8 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
                     }
                 }
             }
-            wave_argmax_step(best, bj);
-            scanned += (uint64_t)V;
+            if (Vs) wave_argmax_step(best, bj);  // (a stored pick: every lane holds it)
+            scanned += (uint64_t)Vs;
             bj_out = bj;
             // the winner's lane holds its tag: its own best is the wave's (lowest j among equals)
             wtag = __builtin_amdgcn_readlane(btag, __builtin_amdgcn_readfirstlane((bj & 255) >> 2));
@@ -804,16 +815,20 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
         d.res_v[e] = res.v;
         d.res_t[e] = res.t;
         ctr_arr[e] = rs.ctr;
-        d.gstats[(long)e * GST + 1] += scanned;
-        d.gstats[(long)e * GST + 2] += (uint64_t)depth;
-        d.gstats[(long)e * GST + 7] += 1;
-        d.gstats[(long)e * GST + 8] += gathered;
+        // no-return atomics: nothing at the end of the game's chain waits for a counter's round trip
+        unsigned long long* gs = reinterpret_cast<unsigned long long*>(d.gstats + (long)e * GST);
+        atomicAdd(gs + 1, (unsigned long long)scanned);
+        atomicAdd(gs + 2, (unsigned long long)depth);
+        atomicAdd(gs + 7, 1ull);
+        atomicAdd(gs + 8, (unsigned long long)gathered);
     }
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr) {
     const int lane = threadIdx.x & 63;
-    const int e = d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6);
+    // the wave's game as a scalar: every per-game base address is then scalar arithmetic, which keeps
+    // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
+    const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));
     if (e >= d.e_hi) return;
     select_game(d, e, lane, env_ids, ctr_arr);
 }
@@ -825,7 +840,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
     EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr) {
     const int lane = threadIdx.x & 63;
-    const int e = d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6);
+    const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
     if (d.done[e]) return;
     expand_backup_game(d, e, lane);
@@ -1001,6 +1016,11 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             // (MCTS.py:90-107).  Written in compact order (coalesced), recomputing each prior
             // exactly as above from the L2-resident logits row (or the hash).
             const float* __restrict__ xr = d.logits + (long)e * PI_LD;
+            // the node summary: the pick of the node's first UCB scan (Ns = 0: every term is
+            // u = (c p) sqe0, the scan's own operations and order), from the final p's
+            const float sqe0 = (float)sqrt((double)0u + 1e-8);
+            float fb = -INFINITY;
+            int fj = 0x7FFFFFFF;
             for (int j0 = lane; j0 < VP; j0 += 256) {  // four gathers in flight per lane
                 float xa[4];
                 int aa[4];
@@ -1018,12 +1038,18 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                         if (j < V) {
                             const float pa = d.prior == 0 ? softmax_p(xa[u], mx, lse) : hash_prior_pi(hsh, aa[u]);
                             p = sum > 0.0f ? pa / sum : inv_fallback;
+                            const float u0 = (d.c32 * p) * sqe0;
+                            if (u0 > fb) {  // ascending j within the lane: strict '>' keeps the lowest
+                                fb = u0;
+                                fj = j;
+                            }
                         }
                         P[j] = p;
                         S[j] = 0;
                     }
                 }
             }
+            wave_argmax_step(fb, fj);  // the largest u0, the lowest index among equals
             if (lane == 0) {
                 NodeRec r;
 #pragma unroll
@@ -1033,7 +1059,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                 r.p_off = off;
                 r.nvalid = (uint32_t)V;
                 r.Ns = 0;
-                r.pad = 0;
+                r.first_j = (uint32_t)fj;
                 d.nodes[g][(long)t * d.NCAP + nid] = r;
                 if (!insert_index(d, g, t, ihsh, nid)) atomicOr(d.err, ERR_HASH);
             }
@@ -1041,11 +1067,11 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             if (lane == 0) {
                 d.node_count[g * d.T + t] = nid + 1;
                 d.arena_top[t] = off + (uint32_t)VP;
-                uint64_t* gs = d.gstats + (long)e * GST;
-                gs[0] += 1;
-                gs[3] += (uint64_t)V;
-                if (nid + 1 > gs[4]) gs[4] = nid + 1;
-                if (off + VP > gs[6]) gs[6] = off + VP;
+                unsigned long long* gs = reinterpret_cast<unsigned long long*>(d.gstats + (long)e * GST);
+                atomicAdd(gs + 0, 1ull);
+                atomicAdd(gs + 3, (unsigned long long)V);
+                atomicMax(gs + 4, (unsigned long long)(nid + 1));
+                atomicMax(gs + 6, (unsigned long long)(off + (uint32_t)VP));
             }
         }
         res = PyV{-(double)v, T_F32};  // return -v  (MCTS.py:115)
@@ -1096,8 +1122,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
         }
         if (lane == 0) {
             d.edge_count[g * d.T + t] = ne1;
-            uint64_t* gs = d.gstats + (long)e * GST;
-            if (ne1 > gs[5]) gs[5] = ne1;
+            atomicMax(reinterpret_cast<unsigned long long*>(d.gstats + (long)e * GST) + 5, (unsigned long long)ne1);
             // a new edge at level 0 (the move's root): into the root's visited list (root_scan)
             if (is_new && eid < (uint32_t)d.ECAP && eid < 65535u) {
                 const uint32_t n = d.root_c[2 * t + 1].z;
@@ -1786,6 +1811,10 @@ constexpr int YK_FPARTS_MAX = 4;
         eng->root_scan = !(ev && ev[0] == '0');
         const char* ek = getenv("YK_ROOT_K");  // a shorter kept order (>= 1): the tests' fallback cases
         d.ro_k = ek ? std::max(1, std::min(RO_K, atoi(ek))) : RO_K;
+        // YK_NODE_SUMMARY=0: a node's first scan is a full scan too (A/B, and the test that both give
+        // the same trees; the records' first_j is written either way)
+        const char* en = getenv("YK_NODE_SUMMARY");
+        d.node_summary = (en && en[0] == '0') ? 0 : 1;
         // YK_SPLIT_DESCENT=1 (measurement): k_expand_backup stops after the backup and each next
         // descent is its own k_select launch, so rocprofv3 times and counts the expansion + backup
         // and the descent apart (the same work: the trees are identical)
