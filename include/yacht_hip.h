@@ -326,6 +326,24 @@ int yk_trainer_apply(yk_trainer_t* t, void* stream);
  * grad norm (nothing can change the buffer between the two), so apply does not re-read it */
 int yk_trainer_step(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
                     const int32_t* batch_idx, int batch, void* stream);
+/* The same two calls with soft policy targets: the loss's policy term is cross_entropy(logits, pi)
+ * with probability targets (mean over the batch) - the full MCTS visit policy instead of its
+ * argmax; a departure from the reference (NNet.py:145-146), opt-in.  pi is the DEVICE CSR
+ * yk_examples_policies writes: batch row i uses CSR row batch_idx[i] (row i when batch_idx is
+ * NULL), entries pi_indptr[r] .. pi_indptr[r+1]-1, pi_cols ascending, pi_vals float64 - each
+ * rounded to float32 once (as torch.as_tensor(pi).float()).  Per row, with s = the float32 sum of
+ * its entries in CSR order: CE = sum_k p_k (lse - z[a_k]), dlogit[a] = (s softmax[a] - p[a]) / batch.
+ * s is not assumed to be 1; a row without entries has CE 0 and no policy gradient; an entry whose
+ * column is outside 0..3225 is ignored; a one-hot row (p = 1.0) is yk_trainer_backward's
+ * arithmetic bit for bit.  Value loss, clip, AdamW, GradScaler and dropout as above;
+ * yk_trainer_losses out[0] = sum_i CE_i.  NULL states / pi_indptr / pi_cols / pi_vals / values or
+ * a batch outside 1..max_batch: YK_ERR_ARG, before anything touches the device. */
+int yk_trainer_backward_soft(yk_trainer_t* t, const yk_state_t* states, const int64_t* pi_indptr,
+                             const int32_t* pi_cols, const double* pi_vals, const float* values,
+                             const int32_t* batch_idx, int batch, void* stream);
+int yk_trainer_step_soft(yk_trainer_t* t, const yk_state_t* states, const int64_t* pi_indptr, const int32_t* pi_cols,
+                         const double* pi_vals, const float* values, const int32_t* batch_idx, int batch,
+                         void* stream);
 /* HOST out[3]: sum over the last batch of cross-entropy, of squared value error; grad sq-norm */
 int yk_trainer_losses(yk_trainer_t* t, double* out);
 /* a reporting epoch's "Avg Loss" (NNet.py:150-160) without a host round trip per minibatch:

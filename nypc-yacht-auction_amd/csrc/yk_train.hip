@@ -3,7 +3,7 @@
 //
 // Per minibatch: gather (features from packed states, hard targets, values) -> forward with the
 // activations the backward needs -> loss = CE(logits, argmax(pi)) + vloss_weight * MSE(v, z)
-// (NNet.py:143-148) -> backward -> [caller all-reduces the gradient buffer for DDP] ->
+// (NNet.py:143-148; yk_trainer_*_soft: CE against the full visit policy, k_loss<true>) -> backward -> [caller all-reduces the gradient buffer for DDP] ->
 // clip_grad_norm_(5.0) (NNet.py:152-153) -> AdamW (NNet.py:109-110).
 //
 // The dense layers are plain GEMMs on a hand-written f32 MFMA kernel (k_sgemm:
@@ -15,6 +15,7 @@
 // buffers in torch state_dict order, so the gradient buffer is one RCCL all-reduce.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "yk_api.h"
@@ -182,16 +183,37 @@ __global__ void k_heads_fwd(const float* Hh, const float* gp, const float* bp, c
 //   Zv1 += bv1 (saved); v = tanh(silu(Zv1) . wv2 + bv2); mse_i = (v - z)^2
 //   logits += bpi; ce_i = lse - logit[t]; dlogits = (softmax - onehot(t)) / B
 //   dzv2 = vw * 2 (v - z) / B * (1 - v^2); dZv1 = dzv2 wv2 silu'(Zv1)
+// SOFT (yk_trainer_*_soft): the target is the row's visit policy p (CSR entries of replay entry
+// idx[row]) instead of onehot(t): the row's dense p staged in LDS (zeroed, then the entries
+// scattered), dlogits = (s softmax - p) / B with s = sum p (psum, k_gather_soft), ce_i = sum_k
+// p_k (lse - logit[a_k]).  A one-hot row repeats the hard arithmetic bit for bit (1.0f x - 1.0f).
 constexpr int LOSS_T = 256;
 constexpr int LOSS_NV = (ASIZE + LOSS_T - 1) / LOSS_T;  // logits per thread
+// The target argument: the gathered hard labels, or (SOFT) the CSR with the batch's replay indices.
+// The variant is a template parameter, so the hard-target kernel is the code it was without it.
+struct SoftRows {
+    SoftCsr csr;
+    const int32_t* idx;
+};
+template <bool SOFT>
+using LossTgt = std::conditional_t<SOFT, SoftRows, const int32_t*>;
+template <bool SOFT>
 __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const float* bpi, float* Zv1, const float* bv1,
-                                                 const float* wv2, const float* bv2, const int32_t* tgt,
+                                                 const float* wv2, const float* bv2, LossTgt<SOFT> tgt,
                                                  const float* vt, float* dlogits, float* dZv1, float* dzv2,
                                                  float* v2prod, float* vout, float2* lrow, int B, int A, float vw) {
     __shared__ float red[2][LOSS_T / 64];
+    __shared__ float pd[SOFT ? ASIZE : 1];  // SOFT: the row's dense target
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (row >= B) return;
     const float* z = logits + (long)row * A;
+    int64_t a0 = 0, a1 = 0;  // SOFT: the row's CSR entries
+    if constexpr (SOFT) {
+        const int64_t src = tgt.idx ? tgt.idx[row] : row;
+        a0 = tgt.csr.indptr[src];
+        a1 = tgt.csr.indptr[src + 1];
+        for (int a = tid; a < ASIZE; a += LOSS_T) pd[a] = 0.0f;
+    }
     float x[LOSS_NV];
     float m = -INFINITY;
 #pragma unroll
@@ -204,6 +226,12 @@ __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const floa
     if (lane == 0) red[0][w] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    if constexpr (SOFT) {  // (pd is zero past the barrier above; the next one publishes the entries)
+        for (int64_t k = a0 + tid; k < a1; k += LOSS_T) {
+            const int c = tgt.csr.cols[k];
+            if ((unsigned)c < (unsigned)ASIZE) pd[c] = soft_p(tgt.csr, k, c);
+        }
+    }
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < LOSS_NV; k++) se += expf(x[k] - m);
@@ -212,15 +240,36 @@ __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const floa
     __syncthreads();
     se = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
     const float lse = m + logf(se);
-    const int t = tgt[row];
+    int t = 0;
+    if constexpr (!SOFT) t = tgt[row];
     const float invB = 1.0f / (float)B;
+    float ce = 0.f, zt = 0.f;
+    if constexpr (SOFT) {
+        const float s = tgt.csr.psum[row];
 #pragma unroll
-    for (int k = 0; k < LOSS_NV; k++) {
-        const int a = tid + LOSS_T * k;
-        if (a < A) dlogits[(long)row * A + a] = (expf(x[k] - lse) - (a == t ? 1.0f : 0.0f)) * invB;
+        for (int k = 0; k < LOSS_NV; k++) {  // (one expression: a one-hot row gives (1.0f x - 1.0f) / B, the hard value)
+            const int a = tid + LOSS_T * k;
+            if (a < A) dlogits[(long)row * A + a] = (s * expf(x[k] - lse) - pd[a]) * invB;
+        }
+        float c = 0.f;
+        for (int64_t k = a0 + tid; k < a1; k += LOSS_T) {
+            const int a = tgt.csr.cols[k];
+            if ((unsigned)a < (unsigned)ASIZE) c += soft_p(tgt.csr, k, a) * (lse - (z[a] + bpi[a]));
+        }
+        c = wsum(c);
+        if (lane == 0) red[0][w] = c;
+        __syncthreads();
+        if (w != 0) return;
+        ce = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < LOSS_NV; k++) {
+            const int a = tid + LOSS_T * k;
+            if (a < A) dlogits[(long)row * A + a] = (expf(x[k] - lse) - (a == t ? 1.0f : 0.0f)) * invB;
+        }
+        if (w != 0) return;
+        zt = z[t] + bpi[t];  // the target logit (the same sum as x[k] where a == t)
     }
-    if (w != 0) return;
-    const float zt = z[t] + bpi[t];  // the target logit (the same sum as x[k] where a == t)
     // value head tail (128 hidden, 2 per lane)
     float s = 0.f, zz[2];
 #pragma unroll
@@ -243,7 +292,7 @@ __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const floa
     if (lane == 0) {  // the per-row losses; k_colsums sums them (no contended atomics)
         dzv2[row] = dv;
         vout[row] = v;
-        lrow[row] = make_float2(lse - zt, e * e);
+        lrow[row] = make_float2(SOFT ? ce : lse - zt, e * e);
     }
 }
 
@@ -386,6 +435,31 @@ __global__ void k_gather(const yk_state_t* states, const int32_t* tgt_all, const
         vt[i] = v_all[src];
     }
 }
+// the soft-target gather: no hard target; the wave of row i also sums the row's probabilities
+// (csr.psum[i] = s_i, once per row per batch; k_loss<true> reads it)
+__global__ void k_gather_soft(const yk_state_t* states, SoftCsr csr, const float* v_all, const int32_t* idx, float* X,
+                              float* vt, int B) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * 64) return;
+    const int i = t >> 6, f = t & 63;
+    const int src = idx ? idx[i] : i;
+    if (f < FEAT) {
+        const uint4* q = reinterpret_cast<const uint4*>(states + src);
+        YkS s;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint4 u = q[k];
+            s.w[2 * k] = (uint64_t)u.x | ((uint64_t)u.y << 32);
+            s.w[2 * k + 1] = (uint64_t)u.z | ((uint64_t)u.w << 32);
+        }
+        X[(long)i * FEAT + f] = feature(s, f);
+    }
+    const float sp = soft_row_sum(csr, csr.indptr[src], csr.indptr[(int64_t)src + 1], f);
+    if (f == 0) {
+        csr.psum[i] = sp;
+        vt[i] = v_all[src];
+    }
+}
 // sum of squares of the gradient buffer: one double partial per workgroup (no atomics); k_adamw
 // adds the SQ_BLOCKS partials in a fixed order
 constexpr int SQ_BLOCKS = 1024;
@@ -463,6 +537,7 @@ struct yk_trainer {
     // activations (Bmax rows)
     float *X = nullptr, *vt = nullptr, *vout = nullptr;
     int32_t* tgt = nullptr;
+    float* psum = nullptr;  // soft targets: each batch row's sum of probabilities (k_gather_soft)
     float *Z0 = nullptr, *mu0 = nullptr, *rs0 = nullptr;
     uint8_t* mask0 = nullptr;
     std::vector<float*> Hs, U1, U2, R1, mu1, rs1, mu2, rs2;
@@ -651,8 +726,8 @@ int gemm_rm(hipStream_t s, float* ws, bool ta, bool tb, int M, int N, int K, con
 }
 
 template <int VPL>
-int step_impl(yk_trainer* t, const yk_state_t* states, const int32_t* targets, const float* values, const int32_t* idx,
-              int B, hipStream_t s) {
+int step_impl(yk_trainer* t, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft, const float* values,
+              const int32_t* idx, int B, hipStream_t s) {
     constexpr int H = VPL * 64;
     const int NB = t->NB, A = ASIZE;
     const float p = t->cfg.dropout;
@@ -661,8 +736,17 @@ int step_impl(yk_trainer* t, const yk_state_t* states, const int32_t* targets, c
     auto Gt = [&](int k) { return t->G + t->off[k]; };
     const dim3 rows((B + 3) / 4), wave4(256);
     int rc;
-    hipLaunchKernelGGL(k_gather, dim3((B * 64 + 255) / 256), dim3(256), 0, s, states, targets, values, idx, t->X, t->tgt,
-                       t->vt, B);
+    SoftCsr sv{};  // the soft launches' argument: the caller's CSR and this trainer's per-row scratch
+    if (soft) {
+        sv = *soft;
+        sv.psum = t->psum;
+    }
+    if (soft)
+        hipLaunchKernelGGL(k_gather_soft, dim3((B * 64 + 255) / 256), dim3(256), 0, s, states, sv, values, idx, t->X,
+                           t->vt, B);
+    else
+        hipLaunchKernelGGL(k_gather, dim3((B * 64 + 255) / 256), dim3(256), 0, s, states, targets, values, idx, t->X,
+                           t->tgt, t->vt, B);
     YK_LAUNCHED();
     // ---- forward
     if ((rc = gemm_rm(s, t->gws, false, true, B, H, FEAT, t->X, FEAT, Pt(T_WIN), FEAT, t->Z0, H, 0.f))) return rc;
@@ -687,9 +771,14 @@ int step_impl(yk_trainer* t, const yk_state_t* states, const int32_t* targets, c
     YK_LAUNCHED();
     if ((rc = gemm_rm(s, t->gws, false, true, B, A, H, t->Api, H, Pt(t_head(NB, 2)), H, t->logits, A, 0.f))) return rc;
     if ((rc = gemm_rm(s, t->gws, false, true, B, 128, H, t->Av, H, Pt(t_head(NB, 6)), H, t->Zv1, 128, 0.f))) return rc;
-    hipLaunchKernelGGL(k_loss, dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1, Pt(t_head(NB, 7)),
-                       Pt(t_head(NB, 8)), Pt(t_head(NB, 9)), t->tgt, t->vt, t->dlogits, t->dZv1, t->dzv2, t->v2prod,
-                       t->vout, t->lrow, B, A, t->cfg.vloss_weight);
+    if (soft)
+        hipLaunchKernelGGL(k_loss<true>, dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1,
+                           Pt(t_head(NB, 7)), Pt(t_head(NB, 8)), Pt(t_head(NB, 9)), SoftRows{sv, idx}, t->vt,
+                           t->dlogits, t->dZv1, t->dzv2, t->v2prod, t->vout, t->lrow, B, A, t->cfg.vloss_weight);
+    else
+        hipLaunchKernelGGL(k_loss<false>, dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1, Pt(t_head(NB, 7)),
+                           Pt(t_head(NB, 8)), Pt(t_head(NB, 9)), t->tgt, t->vt, t->dlogits, t->dZv1, t->dzv2, t->v2prod,
+                           t->vout, t->lrow, B, A, t->cfg.vloss_weight);
     YK_LAUNCHED();
     // ---- backward: heads (bias / LayerNorm gradients are column sums, taken at the end)
     if ((rc = gemm_rm(s, t->gws, true, false, A, H, B, t->dlogits, A, t->Api, H, Gt(t_head(NB, 2)), H, 0.f))) return rc;
@@ -779,6 +868,7 @@ int yk_trainer_create(yk_trainer_t** out, int H, int NB, const float* const* par
     TA(t->X, Bm * FEAT);
     if (!cfg->amp) TA(t->gws, GEMM_WS);
     TA(t->tgt, Bm);
+    if (!cfg->amp) TA(t->psum, Bm);
     TA(t->vt, Bm);
     TA(t->vout, Bm);
     TA(t->Z0, Bm * HH);
@@ -905,16 +995,17 @@ int yk_trainer_buffers(yk_trainer_t* t, float** params, float** grads, int64_t* 
     return YK_OK;
 }
 
-static int backward_impl(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
-                         const int32_t* batch_idx, int batch, bool fuse_norm, hipStream_t s) {
+// targets: the hard labels, or - soft given - unused (the CSR's visit policies are the targets)
+static int backward_impl(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
+                         const float* values, const int32_t* batch_idx, int batch, bool fuse_norm, hipStream_t s) {
     if (t->amp)
-        return yk::amp_backward(t->amp, states, targets, values, batch_idx, batch, t->cfg.dropout, t->cfg.seed, t->step,
-                                t->row_base, t->cfg.vloss_weight, t->lrow, t->lsum, fuse_norm, s);
+        return yk::amp_backward(t->amp, states, targets, soft, values, batch_idx, batch, t->cfg.dropout, t->cfg.seed,
+                                t->step, t->row_base, t->cfg.vloss_weight, t->lrow, t->lsum, fuse_norm, s);
     switch (t->H) {
-        case 64: return step_impl<1>(t, states, targets, values, batch_idx, batch, s);
-        case 128: return step_impl<2>(t, states, targets, values, batch_idx, batch, s);
-        case 256: return step_impl<4>(t, states, targets, values, batch_idx, batch, s);
-        case 512: return step_impl<8>(t, states, targets, values, batch_idx, batch, s);
+        case 64: return step_impl<1>(t, states, targets, soft, values, batch_idx, batch, s);
+        case 128: return step_impl<2>(t, states, targets, soft, values, batch_idx, batch, s);
+        case 256: return step_impl<4>(t, states, targets, soft, values, batch_idx, batch, s);
+        case 512: return step_impl<8>(t, states, targets, soft, values, batch_idx, batch, s);
     }
     return YK_ERR_ARG;
 }
@@ -928,12 +1019,13 @@ __global__ void k_epoch_loss(const float* lsum, double* eloss, double b, double 
     }
 }
 
-static int backward_call(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
-                         const int32_t* batch_idx, int batch, bool fuse_norm, void* stream) {
-    if (!t || !states || !targets || !values) return YK_ERR_ARG;
+static int backward_call(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
+                         const float* values, const int32_t* batch_idx, int batch, bool fuse_norm, void* stream) {
+    if (!t || !states || !values) return YK_ERR_ARG;
+    if (soft ? (!soft->indptr || !soft->cols || !soft->vals) : !targets) return YK_ERR_ARG;
     if (batch <= 0 || batch > t->Bmax) return YK_ERR_ARG;
     hipStream_t s = as_stream(stream);
-    int rc = backward_impl(t, states, targets, values, batch_idx, batch, fuse_norm, s);
+    int rc = backward_impl(t, states, targets, soft, values, batch_idx, batch, fuse_norm, s);
     t->row_base = 0;  // the offset applies to the one backward it was set for (yk_trainer_set_row_offset)
     if (rc == YK_OK && t->eloss_on) {
         hipLaunchKernelGGL(k_epoch_loss, dim3(1), dim3(64), 0, s, t->lsum, t->eloss, (double)batch, t->eloss_vw);
@@ -944,7 +1036,14 @@ static int backward_call(yk_trainer_t* t, const yk_state_t* states, const int32_
 
 int yk_trainer_backward(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
                         const int32_t* batch_idx, int batch, void* stream) {
-    return backward_call(t, states, targets, values, batch_idx, batch, false, stream);
+    return backward_call(t, states, targets, nullptr, values, batch_idx, batch, false, stream);
+}
+
+int yk_trainer_backward_soft(yk_trainer_t* t, const yk_state_t* states, const int64_t* pi_indptr,
+                             const int32_t* pi_cols, const double* pi_vals, const float* values,
+                             const int32_t* batch_idx, int batch, void* stream) {
+    const SoftCsr soft{pi_indptr, pi_cols, pi_vals, nullptr, nullptr};
+    return backward_call(t, states, nullptr, &soft, values, batch_idx, batch, false, stream);
 }
 
 int yk_trainer_epoch_loss_begin(yk_trainer_t* t, double vloss_weight) {
@@ -986,7 +1085,16 @@ int yk_trainer_apply(yk_trainer_t* t, void* stream) {
 int yk_trainer_step(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
                     const int32_t* batch_idx, int batch, void* stream) {
     // (one call, nothing between backward and apply: the gradient launches sum the norm themselves)
-    int rc = backward_call(t, states, targets, values, batch_idx, batch, true, stream);
+    int rc = backward_call(t, states, targets, nullptr, values, batch_idx, batch, true, stream);
+    if (rc) return rc;
+    return yk_trainer_apply(t, stream);
+}
+
+int yk_trainer_step_soft(yk_trainer_t* t, const yk_state_t* states, const int64_t* pi_indptr, const int32_t* pi_cols,
+                         const double* pi_vals, const float* values, const int32_t* batch_idx, int batch,
+                         void* stream) {
+    const SoftCsr soft{pi_indptr, pi_cols, pi_vals, nullptr, nullptr};
+    int rc = backward_call(t, states, nullptr, &soft, values, batch_idx, batch, true, stream);
     if (rc) return rc;
     return yk_trainer_apply(t, stream);
 }

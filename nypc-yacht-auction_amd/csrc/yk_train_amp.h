@@ -11,6 +11,35 @@ namespace yk {
 
 struct AmpTrain;  // device buffers of the mixed-precision step (fp16 weight copies, saved activations)
 
+// Soft policy targets (yk_trainer_*_soft): the visit policies as the device CSR yk_examples_policies
+// writes.  Batch row i's entries are indptr[src] .. indptr[src + 1] - 1 of replay entry src.
+struct SoftCsr {
+    const int64_t* indptr;
+    const int32_t* cols;
+    const double* vals;
+    float* psum;    // trainer scratch: [batch] each row's sum of probabilities s_i
+    int64_t* pcut;  // (amp) [batch][BQ + 1]: where the head-backward parts' runs of a row begin
+};
+// entry k's probability as a float32 tensor holds it (torch.as_tensor(pi).float()); 0 for an
+// entry whose column is not an action (ignored everywhere)
+__device__ __forceinline__ float soft_p(const SoftCsr& c, int64_t k, int col) {
+    return (unsigned)col < (unsigned)YK_ACTION_SIZE ? (float)c.vals[k] : 0.0f;
+}
+// s_i = the float32 sum of a row's probabilities in CSR order, by one wave: 64 entries load at
+// once, the adds run in entry order (a lane past the row adds +0).  The same value on every lane.
+__device__ __forceinline__ float soft_row_sum(const SoftCsr& c, int64_t a0, int64_t a1, int lane) {
+    float s = 0.0f;
+    for (int64_t b = a0; b < a1; b += 64) {
+        const int64_t k = b + lane;
+        float v = 0.0f;
+        if (k < a1) v = soft_p(c, k, c.cols[k]);
+#pragma unroll
+        for (int j = 0; j < 64; j++)
+            s += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+    }
+    return s;
+}
+
 // P / G: the trainer's flat f32 parameter and gradient buffers in YachtNNet.state_dict() order,
 // off[k]: offset of tensor k.  init_scale / growth_interval: GradScaler('cuda') (65536, 2000).
 int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, const long* off, float init_scale,
@@ -23,8 +52,10 @@ int amp_pack(AmpTrain* a, hipStream_t s);
 // lsum = their column sums.  Dropout masks: rows are numbered row_base + i.  fuse_norm: the
 // gradient launches also sum the unscaled sq-norm, and the next amp_apply uses it instead of
 // re-reading G (only when nothing changes G in between: yk_trainer_step, not the DDP split).
-int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const float* values,
-                 const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
+// soft: the visit policies as targets (cross-entropy with probability targets; `targets` unused),
+// or null for the hard labels.
+int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
+                 const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
                  float vloss_weight, float2* lrow, float* lsum, bool fuse_norm, hipStream_t s);
 // GradScaler.unscale_ + clip_grad_norm_(max_norm) + AdamW step (skipped, with the scale halved,
 // when a gradient is inf / nan) + GradScaler.update + fp16 repack.  sq_out: the unscaled grad

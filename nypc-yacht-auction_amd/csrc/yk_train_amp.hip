@@ -26,12 +26,16 @@
 //   k_amp_update   clip + AdamW (or skip), GradScaler update and the fp16 weight copies for the
 //                  next step, a 32 x 32 weight tile (or a vector slice) per workgroup; extra blocks
 //                  make the next step's dropout keep bits (k_amp_masks when they could not)
+// Soft policy targets (yk_trainer_*_soft; the visit policies' CSR in place of the hard labels) are
+// a compile-time variant of k_amp_head (its value part prepares each row's sum and runs) and of
+// k_amp_headbwd / loss_row; the hard instantiations are the code they were without it.
 // Weight fragments use yk_net.h's packing (one plane): for W[N][K], the 1 KB piece (nt, ks) holds
 // W[16 nt + (l & 15)][32 ks + 8 (l >> 4) + j] for lane l, j < 8.  The T layout of an activation
 // matrix X[rows][C] is the same packing of X^T (piece (ct, rs): X[32 rs + 8 (l >> 4) + j][16 ct +
 // (l & 15)]), so dW = dU^T X is an MFMA over 32-row slices with both operands read whole.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "yk_api.h"
@@ -615,8 +619,42 @@ __global__ __launch_bounds__(TTHR) void k_amp_fwd(AmpDev d, const yk_state_t* __
 // ------------------------------------------------------------------ heads
 // policy logits = fp16(a_pi16 Wpi16^T + bpi16) over this part's column tiles, and per row the
 // part's (max, sum exp); part HQ: v_head.2 z1 = fp16(a_v16 Wv1^T + bv1_16)
-template <int H>
-__global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B) {
+// Soft targets, once per batch row (one wave): psum[row] = s = the float32 sum of the row's
+// probabilities in CSR order, and pcut[row][q], q <= BQ = the absolute CSR position of the row's
+// first entry whose column is >= head-backward part q's first action (q = BQ: >= ASIZE), by
+// binary search over the ascending columns (lane q searches cut q).  Part q's entries are then
+// the contiguous run pcut[q] .. pcut[q + 1] - 1; whatever the columns hold, a cut stays inside the row.
+__device__ __forceinline__ void soft_row_prep(const SoftCsr& c, const int32_t* __restrict__ idx,
+                                              int row, int lane) {
+    const int64_t src = idx ? idx[row] : row;
+    const int64_t a0 = c.indptr[src], a1 = c.indptr[src + 1];
+    if (lane <= BQ) {
+        const int first = lane < BQ ? 32 * (lane * PKS / BQ) : ASIZE;
+        int64_t lo = a0, hi = a1 > a0 ? a1 : a0;
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (c.cols[mid] < first) lo = mid + 1;
+            else hi = mid;
+        }
+        c.pcut[(long)row * (BQ + 1) + lane] = lo;
+    }
+    const float s = soft_row_sum(c, a0, a1, lane);
+    if (lane == 0) c.psum[row] = s;
+}
+
+// Soft: nothing (hard targets), or (SoftCsr, const int32_t* idx): part HQ then also prepares the
+// tile's rows' targets (soft_tile_prep).  Without the pack the kernel is the code it was before it.// the tile's 16 rows, two per wave
+__device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int lane, const SoftCsr& c,
+                                               const int32_t* __restrict__ idx) {
+#pragma unroll
+    for (int k = 0; k < TR / TW; k++) {
+        const int row = row0 + wave + TW * k;
+        if (row < B) soft_row_prep(c, idx, row, lane);
+    }
+}
+
+template <int H, class... Soft>
+__global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft) {
     constexpr int SA = H + 8, KS = H / 32;
     __shared__ __attribute__((aligned(16))) _Float16 A[TR * SA];
     __shared__ float2 red[TW][TR];
@@ -645,6 +683,7 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B) {
             const int row = row0 + 4 * q + j;
             if (row < B) d.zv1[(long)row * VH + col] = r16(acc[j] + bias);
         }
+        if constexpr (sizeof...(Soft) > 0) soft_tile_prep(row0, B, wave, lane, soft...);
         return;
     }
     const int t0 = part * PT / HQ, t1 = (part + 1) * PT / HQ;
@@ -731,7 +770,10 @@ __device__ __forceinline__ float row_lse(const AmpDev& d, int row) {
 // One example's losses (one wave): cross-entropy from the row's log-sum-exp; the fp16 value-head
 // tail (SiLU, Linear(128, 1), tanh), the MSE and their backward into dz1 / v_head.4's product
 // terms; rows past the batch (up to the 32-row slice) zero their dz1 T-layout entries.
-__device__ __forceinline__ void loss_row(const AmpDev& d, const int32_t* __restrict__ tgt_all,
+// SOFT: the cross-entropy against the row's visit policy, ce = sum_k p_k (lse - logit[a_k]) over
+// the row's CSR entries (the lanes stride them; a one-hot row: 1.0f (lse - logit[t]), the hard value)
+template <bool SOFT, class Tgt>
+__device__ __forceinline__ void loss_row(const AmpDev& d, const Tgt& tgt_all,
                                          const float* __restrict__ v_all, const int32_t* __restrict__ idx, int B,
                                          float vw, float2* __restrict__ lrow, int row, int lane) {
     if (row >= d.RS * 32) return;
@@ -746,10 +788,21 @@ __device__ __forceinline__ void loss_row(const AmpDev& d, const int32_t* __restr
     }
     const float S = d.sc->scale, invB = 1.0f / (float)B;
     const int src = idx ? idx[row] : row;
-    const int t = tgt_all[src];
+    int t = 0;
+    if constexpr (!SOFT) t = tgt_all[src];
     const float z = v_all[src];
     const float lse = row_lse(d, row);
-    const float ce = lse - d.logits[(long)row * LDL + t];
+    float ce = 0.f;
+    if constexpr (!SOFT) ce = lse - d.logits[(long)row * LDL + t];
+    if constexpr (SOFT) {
+        const int64_t a1 = tgt_all.indptr[(int64_t)src + 1];
+        float c = 0.f;
+        for (int64_t k = tgt_all.indptr[src] + lane; k < a1; k += 64) {
+            const int a = tgt_all.cols[k];
+            if ((unsigned)a < (unsigned)ASIZE) c += soft_p(tgt_all, k, a) * (lse - d.logits[(long)row * LDL + a]);
+        }
+        ce = wsum(c);
+    }
     const float* wv2 = d.P + poff(d.H, d.NB, t_head(d.NB, HV_W2));
     const float bv2 = r16(d.P[poff(d.H, d.NB, t_head(d.NB, HV_B2))]);
     float z1[2], s16[2], w2[2];
@@ -789,23 +842,36 @@ __device__ __forceinline__ void loss_row(const AmpDev& d, const int32_t* __restr
 // gradient partial), and dA_pi's split-K partial = dlogits16 Wpi16 over these slices.  One more
 // part per tile runs its loss rows (loss_row, a wave per row; the last tile the slice's rows past
 // it too) beside them - one launch fewer than a separate loss kernel.
-template <int H>
-__global__ __launch_bounds__(TTHR) void k_amp_headbwd(AmpDev d, const int32_t* __restrict__ tgt_all,
+// SOFT (visit-policy targets): dlogits = fp16(S (s softmax - p) / B).  The part's columns of p for
+// the 16 rows are an f32 LDS tile (PD): zeroed, then each row's entries inside the part - one
+// contiguous run of the ascending CSR columns, its ends pcut[row][part], pcut[row][part + 1] found
+// by k_amp_head_soft's binary search - scattered by the row's 32 threads.  All of it sits before
+// the gradient block, where only the ring's first fill is in flight; nothing changes from the
+// block's barrier on (the refills in the MFMA loop stay unconditional).
+// The variant is a template parameter, so the hard-target kernel is the code it was without it.
+template <bool SOFT>
+using AmpTgt = std::conditional_t<SOFT, SoftCsr, const int32_t* __restrict__>;  // the labels, or the CSR
+template <int H, bool SOFT = false>
+__global__ __launch_bounds__(TTHR) void k_amp_headbwd(AmpDev d, AmpTgt<SOFT> tgt_all,
                                                       const float* __restrict__ v_all, const int32_t* __restrict__ idx,
                                                       int B, float vw, float2* __restrict__ lrow) {
     constexpr int NT = H >= 128 ? H / 128 : 1, NACT = H / (16 * NT);
     constexpr int SPMAX = (PKS + BQ - 1) / BQ;
     constexpr int SD = SPMAX * 32 + 8;
+    constexpr int PW = SPMAX * 32;  // PD's row stride
     constexpr int RD = 4;  // weight ring depth (slices)
     __shared__ __attribute__((aligned(16))) _Float16 DL[TR * SD];
     __shared__ float LSE[TR];
-    __shared__ int TG[TR];
+    __shared__ int TG[SOFT ? 1 : TR];
+    __shared__ float PS[SOFT ? TR : 1];       // SOFT: the rows' s
+    __shared__ float PD[SOFT ? TR * PW : 1];  // SOFT: the rows' p over the part's columns
     const int tile = blockIdx.x, part = blockIdx.y, row0 = tile * TR;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     if (part == BQ) {  // the loss part: the tile's rows (and, in the last tile, the slice's rows past it)
 #pragma unroll
         for (int k = 0; k < 2 * TR / TW; k++)
-            if (k < TR / TW || tile == (int)gridDim.x - 1) loss_row(d, tgt_all, v_all, idx, B, vw, lrow, row0 + TW * k + wave, lane);
+            if (k < TR / TW || tile == (int)gridDim.x - 1)
+                loss_row<SOFT>(d, tgt_all, v_all, idx, B, vw, lrow, row0 + TW * k + wave, lane);
         return;
     }
     const int ks0 = part * PKS / BQ, ks1 = (part + 1) * PKS / BQ, ns = ks1 - ks0;
@@ -814,10 +880,20 @@ __global__ __launch_bounds__(TTHR) void k_amp_headbwd(AmpDev d, const int32_t* _
     // a vmcnt(0) there would drain the ring's in-flight refills)
     const bool gw = NACT == TW || wave < NACT;
     const int nt0 = wave * NT;
+    int64_t c0 = 0, c1 = 0;  // SOFT: the run of row tid / 32's entries inside this part
+    if constexpr (SOFT) {
+        for (int i = tid; i < TR * PW; i += TTHR) PD[i] = 0.0f;
+        const int row = row0 + (tid >> 5);
+        if (row < B) {
+            c0 = tgt_all.pcut[(long)row * (BQ + 1) + part];
+            c1 = tgt_all.pcut[(long)row * (BQ + 1) + part + 1];
+        }
+    }
     if (tid < TR) {
         const int row = row0 + tid;
         LSE[tid] = row < B ? row_lse(d, row) : 0.f;
-        TG[tid] = row < B ? tgt_all[idx ? idx[row] : row] : -1;
+        if constexpr (SOFT) PS[tid] = row < B ? tgt_all.psum[row] : 0.f;
+        else TG[tid] = row < B ? tgt_all[idx ? idx[row] : row] : -1;
     }
     // this part's logits first (every thread's, unconditionally, clamped), then the first slices
     // of Wpi^T: the gradient block then waits for the logits only (vmcnt retires in order)
@@ -838,6 +914,14 @@ __global__ __launch_bounds__(TTHR) void k_amp_headbwd(AmpDev d, const int32_t* _
             for (int t = 0; t < NT; t++) ring[s][t] = d.wpit[((long)(nt0 + t) * PKS + min(ks0 + s, PKS - 1)) * 64 + lane];
     }
     __syncthreads();
+    if constexpr (SOFT) {  // (PD is zero past the barrier; an entry outside the part's actions is ignored)
+        const int hi = min(32 * ks0 + W, ASIZE);
+        for (int64_t k = c0 + (tid & 31); k < c1; k += 32) {
+            const int a = tgt_all.cols[k];
+            if (a >= 32 * ks0 && a < hi) PD[(tid >> 5) * PW + a - 32 * ks0] = (float)tgt_all.vals[k];
+        }
+        __syncthreads();
+    }
     const float S = d.sc->scale, invB = 1.0f / (float)B;
 #pragma unroll
     for (int k = 0; k < LPT; k++) {
@@ -845,7 +929,11 @@ __global__ __launch_bounds__(TTHR) void k_amp_headbwd(AmpDev d, const int32_t* _
         if (i < TR * W) {
             const int r = i / W, c = i - r * W, a = 32 * ks0 + c, row = row0 + r;
             float g = 0.f;
-            if (row < B && a < ASIZE) g = r16(S * (expf(lg[k] - LSE[r]) - (a == TG[r] ? 1.0f : 0.0f)) * invB);
+            if constexpr (SOFT) {
+                if (row < B && a < ASIZE) g = r16(S * (PS[r] * expf(lg[k] - LSE[r]) - PD[r * PW + c]) * invB);
+            } else {
+                if (row < B && a < ASIZE) g = r16(S * (expf(lg[k] - LSE[r]) - (a == TG[r] ? 1.0f : 0.0f)) * invB);
+            }
             DL[r * SD + c] = (_Float16)g;
         }
     }
@@ -1697,6 +1785,8 @@ struct AmpTrain {
     float* lsum_src_dummy = nullptr;
     float2* lrow = nullptr;
     float* lsum = nullptr;
+    float* psum = nullptr;    // soft targets: [Bmax] each batch row's sum of probabilities (soft_row_prep)
+    int64_t* pcut = nullptr;  // [Bmax][BQ + 1] the CSR positions where the head-backward parts' runs begin
 };
 
 namespace {
@@ -1782,6 +1872,8 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     AA(d.dpart, (size_t)BQ * Bm * H);
     AA(d.dbpi_part, T * LDL);
     AA(d.colpart, T * d.NVEC * H);
+    AA(a->psum, Bm);
+    AA(a->pcut, Bm * (BQ + 1));
     AA(a->sqpart, (size_t)SQ_BLOCKS);
     AA(a->sc, 1);
     AA(a->sc_next, 1);
@@ -1922,11 +2014,17 @@ int amp_pack(AmpTrain* a, hipStream_t s) {
     return YK_OK;
 }
 
-int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const float* values,
-                 const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
+int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
+                 const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
                  float vloss_weight, float2* lrow, float* lsum, bool fuse_norm, hipStream_t s) {
     if (B <= 0 || B > a->Bmax) return YK_ERR_ARG;
     a->norm_ready = false;
+    SoftCsr sv{};  // the soft launches' argument: the caller's CSR and this trainer's per-row scratch
+    if (soft) {
+        sv = *soft;
+        sv.psum = a->psum;
+        sv.pcut = a->pcut;
+    }
     double* sqp = fuse_norm ? a->sq_items : nullptr;
     AmpDev& d = a->d;
     if (a->lrow != lrow || a->lsum != lsum) {  // the loss-sum job reads the trainer's row losses
@@ -1951,10 +2049,17 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
     case HH:                                                                                                        \
         hipLaunchKernelGGL(k_amp_fwd<HH>, dim3(TT), dim3(TTHR), 0, s, d, states, idx, B, dropout, seed, step, row_base); \
         YK_LAUNCHED();                                                                                              \
-        hipLaunchKernelGGL(k_amp_head<HH>, dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B);                               \
+        if (soft)                                                                                                   \
+            hipLaunchKernelGGL((k_amp_head<HH, SoftCsr, const int32_t*>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, sv, idx); \
+        else                                                                                                        \
+            hipLaunchKernelGGL(k_amp_head<HH>, dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B);                           \
         YK_LAUNCHED();                                                                                              \
-        hipLaunchKernelGGL(k_amp_headbwd<HH>, dim3(T, BQ + 1), dim3(TTHR), 0, s, d, targets, values, idx, B,       \
-                           vloss_weight, lrow);                                                                     \
+        if (soft)                                                                                                   \
+            hipLaunchKernelGGL((k_amp_headbwd<HH, true>), dim3(T, BQ + 1), dim3(TTHR), 0, s, d, sv, values, idx, B,  \
+                               vloss_weight, lrow);                                                                 \
+        else                                                                                                        \
+            hipLaunchKernelGGL(k_amp_headbwd<HH>, dim3(T, BQ + 1), dim3(TTHR), 0, s, d, targets, values, idx, B,   \
+                               vloss_weight, lrow);                                                                 \
         YK_LAUNCHED();                                                                                              \
         hipLaunchKernelGGL(k_amp_bwd<HH>, dim3(TT + (a->n_dw_items - a->n_dw_trunk + TW - 1) / TW), dim3(TTHR), 0, s, \
                            d, B, dropout, seed, step, row_base, a->dw_jobs, a->dw_items + a->n_dw_trunk,          \

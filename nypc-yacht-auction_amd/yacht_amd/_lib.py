@@ -78,6 +78,8 @@ SIGNATURES = {
     "yk_trainer_backward": [P, P, P, P, P, I, P],
     "yk_trainer_apply": [P, P],
     "yk_trainer_step": [P, P, P, P, P, I, P],
+    "yk_trainer_backward_soft": [P, P, P, P, P, P, P, I, P],
+    "yk_trainer_step_soft": [P, P, P, P, P, P, P, I, P],
     "yk_trainer_losses": [P, P],
     "yk_trainer_epoch_loss_begin": [P, C.c_double],
     "yk_trainer_epoch_loss_end": [P, P],
@@ -104,7 +106,8 @@ SIGNATURES = {
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
-_NEWER = {"yk_engine_counters", "yk_net_errors"}  # added in rounds 5-6 (A/B baselines may predate them)
+# added in rounds 5-6 and with the soft policy targets (A/B baselines may predate them)
+_NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft"}
 _lib = None
 
 

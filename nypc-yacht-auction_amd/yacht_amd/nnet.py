@@ -213,11 +213,21 @@ class NNetWrapper:
             all-reduce per step;
           "split": the minibatch split across the ranks, the share-weighted gradients
             all-reduced (DDP): the single-process step up to f32 summation order;
-          "per_rank": every rank its own batch_size rows (a world x batch_size global batch)."""
+          "per_rank": every rank its own batch_size rows (a world x batch_size global batch).
+
+        args.policy_target: "argmax" (default; the reference's hard label, NNet.py:145-146) or
+        "visits" - cross-entropy against the full MCTS visit policy pi = N / sum N (soft targets,
+        F.cross_entropy(out_pi, pi); a departure from the reference), in every ddp_batch mode.
+        It needs the policies: tuples, or shards built by examples_from_images."""
         from . import dist as D
-        from .replay import as_device_examples
+        from .replay import as_device_examples, as_device_policies
+        target = self.args.get("policy_target", "argmax")
+        if target not in ("argmax", "visits"):
+            raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
         tr = self._trainer()
         states, targets, values = as_device_examples(examples)
+        # "visits": the same rows' policies as a CSR; "argmax" calls the trainer exactly as before
+        soft = {"policies": as_device_policies(examples)} if target == "visits" else {}
         rank, world = D.rank_world()
         n = states.shape[0]
         bs = self.args.batch_size
@@ -236,7 +246,7 @@ class NNetWrapper:
             for i in range(0, n, rows):
                 idx = perm[i:i + rows]
                 if mode == "replicated":
-                    tr.step(states, targets, values, idx=idx)
+                    tr.step(states, targets, values, idx=idx, **soft)
                     b = idx.numel()
                 else:
                     parts = torch.tensor_split(idx, world)
@@ -244,7 +254,7 @@ class NNetWrapper:
                     b = loc.numel()
                     row0 = sum(int(x.numel()) for x in parts[:rank])  # this rank's rows in the minibatch
                     if b:
-                        tr.backward(states, targets, values, idx=loc, row0=row0)
+                        tr.backward(states, targets, values, idx=loc, row0=row0, **soft)
                     else:
                         tr.grads().zero_()
                     D.allreduce_grads(tr, weight=b / idx.numel())

@@ -6,8 +6,9 @@ not fit (a dense pi is 3226 floats), and NNetWrapper.train only uses ``argmax(pi
 (NNet.py:145-146).  So an iteration's examples are an ``ExampleShard``: device arrays of
 packed boards (64 B), argmax targets and float32 values, built by ``yk_examples_from_records``
 straight from the (all-gathered) trajectory record images, plus the full visit policies as a
-device CSR (``yk_examples_policies``) for the examples file (Coach.py:144-151) and for code that
-iterates the reference's tuples.  The record images are not kept.
+device CSR (``yk_examples_policies``) for the examples file (Coach.py:144-151), for code that
+iterates the reference's tuples, and for training on them (``policy_target="visits"``:
+``as_device_policies``).  The record images are not kept.
 """
 from __future__ import annotations
 
@@ -136,4 +137,75 @@ def as_device_examples(examples):
     return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
 
 
-__all__ = ["ExampleShard", "examples_from_images", "as_device_examples"]
+# ---------------------------------------------------------------- the full policies (policy_target="visits")
+def _no_policies():
+    return ValueError('policy_target="visits" needs the full policies, and this ExampleShard has none '
+                      "(policies=None): build it with examples_from_images, or train with policy_target=\"argmax\"")
+
+
+def _tuples_csr_host(items):
+    """[(board, pi, v)] with dense pi -> (indptr int64[n+1], cols int32, vals float64): the nonzero
+    entries of every pi, columns ascending (what yk_examples_policies writes for the same rows)."""
+    indptr = np.zeros(len(items) + 1, dtype=np.int64)
+    cols, vals = [], []
+    for k0 in range(0, len(items), 1024):  # (a dense row is 25 KB: a chunk at a time)
+        dense = np.asarray([np.asarray(p, dtype=np.float64) for _, p, _ in items[k0:k0 + 1024]], dtype=np.float64)
+        dense = dense.reshape(len(dense), -1)
+        r, c = np.nonzero(dense)  # row-major: ascending columns within a row
+        indptr[k0 + 1:k0 + 1 + len(dense)] = np.bincount(r, minlength=len(dense))
+        cols.append(c.astype(np.int32))
+        vals.append(dense[r, c])
+    np.cumsum(indptr, out=indptr)
+    return (indptr, np.concatenate(cols) if cols else np.zeros(0, dtype=np.int32),
+            np.concatenate(vals) if vals else np.zeros(0, dtype=np.float64))
+
+
+def _cat_csr(parts, xp):
+    """CSR row blocks -> one CSR: indptr concatenated with each block's entry offset."""
+    parts = [p for p in parts if p[0].shape[0] > 1]  # (as as_device_examples drops empty blocks)
+    if not parts:
+        return None
+    if len(parts) == 1:
+        return parts[0]
+    indptr, off = [parts[0][0][:1] * 0], 0
+    for ip, _, _ in parts:
+        indptr.append(ip[1:] + (off - int(ip[0])))
+        off += int(ip[-1]) - int(ip[0])
+    if xp is np:
+        return np.concatenate(indptr), np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+    return torch.cat(indptr), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])
+
+
+def policies_csr_host(examples):
+    """The full policies of `examples` - an ExampleShard, a list of (board, pi, v) tuples (what
+    load_examples / load_reference_examples return), or a list of either (trainExamplesHistory) -
+    as host CSR arrays (pi_indptr int64[n+1], pi_cols int32, pi_vals float64), for the rows
+    as_device_examples returns, in its order.  Tuple lists need no GPU."""
+    if isinstance(examples, ExampleShard):
+        if examples.policies is None:
+            raise _no_policies()
+        h = examples.host()
+        return h["pi_indptr"], h["pi_cols"], h["pi_vals"]
+    items = list(examples)
+    if not items or _is_example(items[0]):
+        return _tuples_csr_host(items)
+    out = _cat_csr([policies_csr_host(x) for x in items], np)
+    return out if out is not None else _tuples_csr_host([])
+
+
+def as_device_policies(examples):
+    """policies_csr_host on the device: (pi_indptr, pi_cols, pi_vals) tensors, the soft targets
+    Trainer.step(..., policies=) takes.  A shard's CSR is used where it lies (no copy)."""
+    if isinstance(examples, ExampleShard):
+        if examples.policies is None:
+            raise _no_policies()
+        P = examples.policies
+        return P["pi_indptr"], P["pi_cols"], P["pi_vals"]
+    items = list(examples)
+    if not items or _is_example(items[0]):
+        return tuple(torch.from_numpy(a).to("cuda") for a in _tuples_csr_host(items))
+    out = _cat_csr([as_device_policies(x) for x in items], torch)
+    return out if out is not None else as_device_policies([])
+
+
+__all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host"]

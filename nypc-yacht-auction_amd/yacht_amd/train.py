@@ -6,7 +6,8 @@ A ``Trainer`` owns flat device buffers (parameters, gradients, AdamW moments) in
 a minibatch of replay entries; ``backward`` / ``apply`` split it so a DDP all-reduce of the
 gradient buffer (``grads()``, zero-copy torch view) can run in between, as torch DDP does.
 The replay buffer lives on the device as packed boards (64 B), hard targets (argmax of the
-policy, NNet.py:145-146) and values.
+policy, NNet.py:145-146) and values; ``policies=`` trains on the full visit policies instead (soft
+cross-entropy targets from the buffer's CSR, yk_trainer_*_soft; opt-in).
 """
 from __future__ import annotations
 
@@ -66,19 +67,41 @@ class Trainer:
         return torch.as_tensor(_DevView(self._gptr, self.nparams), device="cuda")
 
     # ---- steps
-    def backward(self, states, targets, values, idx=None, batch=None, stream=None, row0=0):
-        """row0: the global row of this batch's first example in the minibatch (dropout masks)."""
+    @staticmethod
+    def _csr(policies):
+        """policies: (pi_indptr int64, pi_cols int32, pi_vals float64) device tensors, or the
+        ExampleShard.policies dict holding them -> their device pointers."""
+        if isinstance(policies, dict):
+            policies = (policies["pi_indptr"], policies["pi_cols"], policies["pi_vals"])
+        indptr, cols, vals = policies
+        if indptr.dtype != torch.int64 or cols.dtype != torch.int32 or vals.dtype != torch.float64:
+            raise TypeError("policies: pi_indptr int64, pi_cols int32, pi_vals float64")
+        # (an empty CSR's cols / vals may have no storage: any non-null pointer does, nothing reads it)
+        return ptr(indptr), ptr(cols) or ptr(indptr), ptr(vals) or ptr(indptr)
+
+    def backward(self, states, targets, values, idx=None, batch=None, stream=None, row0=0, policies=None):
+        """row0: the global row of this batch's first example in the minibatch (dropout masks).
+        policies: train the policy head on the full visit policies (soft cross-entropy targets,
+        the CSR of as_device_policies / ExampleShard.policies) instead of `targets` (may be None)."""
         n = int(batch if batch is not None else (idx.numel() if idx is not None else states.shape[0]))
         call("yk_trainer_set_row_offset", self.handle, int(row0))
+        if policies is not None:
+            call("yk_trainer_backward_soft", self.handle, ptr(states), *self._csr(policies), ptr(values),
+                 ptr(idx) if idx is not None else None, n, stream_ptr(stream))
+            return
         call("yk_trainer_backward", self.handle, ptr(states), ptr(targets), ptr(values),
              ptr(idx) if idx is not None else None, n, stream_ptr(stream))
 
     def apply(self, stream=None):
         call("yk_trainer_apply", self.handle, stream_ptr(stream))
 
-    def step(self, states, targets, values, idx=None, batch=None, stream=None):
+    def step(self, states, targets, values, idx=None, batch=None, stream=None, policies=None):
         n = int(batch if batch is not None else (idx.numel() if idx is not None else states.shape[0]))
         call("yk_trainer_set_row_offset", self.handle, 0)
+        if policies is not None:  # soft targets (see backward)
+            call("yk_trainer_step_soft", self.handle, ptr(states), *self._csr(policies), ptr(values),
+                 ptr(idx) if idx is not None else None, n, stream_ptr(stream))
+            return
         call("yk_trainer_step", self.handle, ptr(states), ptr(targets), ptr(values),
              ptr(idx) if idx is not None else None, n, stream_ptr(stream))
 
