@@ -172,6 +172,13 @@ typedef struct {
                                (2 with the net prior at >= 8192 games, else 1), at most 8 */
     int dual_trees;         /* arena: two trees per game, so MCTS vs MCTS plays two MCTS objects with
                                their own trees and nets (Coach.py:117-125's pmcts / nmcts) */
+    double dirichlet_alpha; /* AlphaZero's root exploration noise, a departure from the reference, opt-in: on */
+    double dirichlet_eps;   /* when alpha > 0 and eps > 0 (default 0, 0: off).  yk_selfplay then replaces each
+                               real move's root prior once, before any UCB scan of that root in the move, by
+                               P'[j] = float32((1 - eps) * (double)P[j] + eps * eta[j]) over the root's valid
+                               actions j (ascending), eta ~ Dir(alpha) = yk_dirichlet_noise(seed, env id, move, V,
+                               alpha).  yk_arena and yk_mcts_search never add noise.  The game's draw stream is
+                               not consumed.  alpha NaN or < 0, eps outside [0, 1]: YK_ERR_ARG */
 } yk_engine_config_t;
 
 typedef struct yk_engine yk_engine_t;
@@ -188,7 +195,8 @@ int yk_selfplay(yk_engine_t* eng, uint64_t seed, uint32_t env_base, void* stream
  * yk_engine_kernel_times (launches counts the timed ones): HOST ms[8],
  * launches[8] for classes 0 first descent of a move, 1 forward (the whole predict), 2 unused,
  * 3 expand + backup + the next descent, 4 move begin (root / tree compaction), 5 move end
- * (policy, sampling, real step). */
+ * (policy, sampling, real step), 6 the root noise (both launches of a move; 0 launches when the noise
+ * is off - with it on and full root scans, simulation 1's descent is its own launch, timed as class 2). */
 int yk_engine_profile(yk_engine_t* eng, int enable);
 int yk_engine_kernel_times(yk_engine_t* eng, double* ms, int64_t* launches);
 /* HOST out[16]: 0 expansions, 1 valid entries scanned by UCB, 2 real moves (max over games),
@@ -217,6 +225,20 @@ int yk_engine_records(yk_engine_t* eng, uint64_t* states, int32_t* info, uint64_
  * v[R][max_expansions], leaves[R][max_expansions] the expanded canonical states, count[R] the
  * expansions of each game (> max_expansions: the record was truncated).  Any may be NULL. */
 int yk_engine_predictions(yk_engine_t* eng, float* pi, float* v, yk_state_t* leaves, int32_t* count);
+/* Root noise of the last yk_selfplay, for the R record_predictions games: HOST before[R][max_moves][3226],
+ * after[R][max_moves][3226] (either may be NULL), dense by action - the prior P of move m's root as the
+ * noise found it and P' as it left it, 0 at invalid actions and for moves >= the game's n_moves.
+ * YK_ERR_STATE unless the engine has both record_predictions and noise on and has played a batch. */
+int yk_engine_root_priors(yk_engine_t* eng, float* before, float* after);
+/* The noise itself: eta[i*3226 + j], j < nvalid[i], is the Dirichlet(alpha) sample over nvalid[i] valid
+ * actions that game env_ids[i] gets at move moves[i] under `seed` (0 for j >= nvalid[i]; nvalid is clamped
+ * to 0..3226) - the same device function as the engine's, so the same bits.  Defined by Philox4x32-10 with
+ * counter (draw i, action j, env, 0x80000000 | move) - the game streams use counter word 3 = 0 - and, in
+ * float64, u = ((x >> 11) + 0.5) 2^-53, a Marsaglia-Tsang gamma per action (alpha < 1: boosted by
+ * u^(1/alpha)) and eta = g / sum g (1 / nvalid when the sum is 0); DESIGN.md section 6d.  DEVICE arrays
+ * env_ids[n], moves[n], nvalid[n], eta[n][3226]; alpha > 0. */
+int yk_dirichlet_noise(uint64_t seed, const uint32_t* env_ids, const int32_t* moves, const int32_t* nvalid,
+                       double alpha, double* eta, int n, void* stream);
 /* Fixed-size trajectory records of the last batch for the multi-GPU all-gather:
  * yk_engine_record_bytes = size of the packed image; yk_engine_pack_records copies it
  * (device to device, async on `stream`) into dst (device, >= that many bytes).  Image:

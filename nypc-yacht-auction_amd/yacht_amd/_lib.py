@@ -37,7 +37,8 @@ class YkEngineConfig(C.Structure):
     _fields_ = [("n_envs", C.c_int), ("sims", C.c_int), ("cpuct", C.c_double), ("temp_threshold", C.c_int),
                 ("max_moves", C.c_int), ("prior", C.c_int), ("record_predictions", C.c_int),
                 ("max_expansions", C.c_int), ("arena_entries", C.c_int64), ("record_stride", C.c_int),
-                ("groups", C.c_int), ("dual_trees", C.c_int)]
+                ("groups", C.c_int), ("dual_trees", C.c_int), ("dirichlet_alpha", C.c_double),
+                ("dirichlet_eps", C.c_double)]
 
 
 # name -> argtypes (restype int unless listed in _RESTYPE)
@@ -96,6 +97,8 @@ SIGNATURES = {
     "yk_engine_kernel_times": [P, P, P],
     "yk_engine_records": [P, P, P, P, P, P, P, P, P, P],
     "yk_engine_predictions": [P, P, P, P, P],
+    "yk_engine_root_priors": [P, P, P],
+    "yk_dirichlet_noise": [U64, P, P, P, C.c_double, P, I, P],
     "yk_engine_record_bytes": [P],
     "yk_engine_pack_records": [P, P, C.c_int64, P],
     "yk_mcts_search": [P, P, U64, P, P, I, P, P],
@@ -106,8 +109,9 @@ SIGNATURES = {
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
-# added in rounds 5-6 and with the soft policy targets (A/B baselines may predate them)
-_NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft"}
+# added in rounds 5-6, with the soft policy targets and with the root noise (A/B baselines may predate them)
+_NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
+          "yk_engine_root_priors", "yk_dirichlet_noise"}
 _lib = None
 
 

@@ -81,7 +81,11 @@ class Coach:
         prior = "hash" if getattr(self.nnet, "yk_prior", None) == "hash" else "net"
         net = None if prior == "hash" else self.nnet.yk_net()
         return SelfPlayEngine(n, self.args.numMCTSSims, self.args.cpuct, self.args.tempThreshold, net=net,
-                              prior=prior, max_moves=GAME_MOVES)
+                              prior=prior, max_moves=GAME_MOVES,
+                              # root exploration noise of self-play (off unless both are set; the gating
+                              # arena and the MCTS plugin never add it)
+                              dirichlet_alpha=self.args.get("dirichletAlpha", 0.0),
+                              dirichlet_eps=self.args.get("dirichletEpsilon", 0.0))
 
     def executeEpisodes(self, n: int):
         """n episodes as the reference's per-game lists of (YachtState, pi, v) (this process only)."""

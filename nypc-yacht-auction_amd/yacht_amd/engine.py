@@ -22,7 +22,8 @@ class SelfPlayEngine:
     def __init__(self, n_envs: int, sims: int, cpuct: float = 1.5, temp_threshold: int = 15, net=None,
                  prior: str = "net", max_moves: int = 64, record_predictions: bool = False,
                  max_expansions: int = 0, arena_entries: int = 0, record_stride: int = 1, groups: int = 0,
-                 dual_trees: bool = False, opponent_net=None):
+                 dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
+                 dirichlet_eps: float = 0.0):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -32,7 +33,9 @@ class SelfPlayEngine:
                                   record_predictions=int(record_predictions),
                                   max_expansions=max_expansions or (max_moves * sims + 8),
                                   arena_entries=arena_entries, record_stride=max(int(record_stride), 1),
-                                  groups=int(groups), dual_trees=int(bool(dual_trees)))
+                                  groups=int(groups), dual_trees=int(bool(dual_trees)),
+                                  # AlphaZero's root noise in run() (never in arena()); on when both are > 0
+                                  dirichlet_alpha=float(dirichlet_alpha), dirichlet_eps=float(dirichlet_eps))
         self.net = net  # keep the weights alive
         h = C.c_void_p()
         call("yk_engine_create", C.byref(h), C.byref(self.cfg), C.c_void_p(net.handle if net is not None else None))
@@ -96,7 +99,10 @@ class SelfPlayEngine:
         ms = np.zeros(8, dtype=np.float64)
         n = np.zeros(8, dtype=np.int64)
         call("yk_engine_kernel_times", self.handle, ms.ctypes.data, n.ctypes.data)
-        return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(self.KERNEL_CLASSES) if k != "unused"}
+        kt = {k: (float(ms[i]), int(n[i])) for i, k in enumerate(self.KERNEL_CLASSES) if k != "unused"}
+        if self.cfg.dirichlet_alpha > 0 and self.cfg.dirichlet_eps > 0:
+            kt["root_noise"] = (float(ms[6]), int(n[6]))  # k_root_noise, two launches per move (class 6)
+        return kt
 
     STAT_NAMES = ("expansions", "scanned", "moves", "errors", "max_nodes", "max_edges", "max_arena", "vnew",
                   "path_edges", "sims", "node_cap", "edge_cap", "arena_cap", "visit_cap", "groups",
@@ -146,6 +152,16 @@ class SelfPlayEngine:
         if (cnt > X).any():
             raise RuntimeError(f"prediction record truncated: {int(cnt.max())} expansions > max_expansions {X}")
         return (pi, v, cnt, lv) if leaves else (pi, v, cnt)
+
+    def root_priors(self):
+        """(before, after), float32[R, max_moves, 3226] dense by action, of the recorded games of the last
+        run(): each move's root prior as the Dirichlet noise found it and as it left it (0 at invalid
+        actions and past the game's end).  Needs record_predictions and the noise on."""
+        R = (self.n_envs + self.cfg.record_stride - 1) // self.cfg.record_stride
+        before = np.zeros((R, self.max_moves, ACTION_SIZE), dtype=np.float32)
+        after = np.zeros_like(before)
+        call("yk_engine_root_priors", self.handle, before.ctypes.data, after.ctypes.data)
+        return before, after
 
     def record_bytes(self) -> int:
         n = int(lib().yk_engine_record_bytes(self.handle))

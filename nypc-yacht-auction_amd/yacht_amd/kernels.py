@@ -140,8 +140,23 @@ def hash_prior(states):
     return pi, v
 
 
+def dirichlet_noise(seed: int, env_ids, moves, nvalid, alpha: float):
+    """The self-play engine's root noise (yk_dirichlet_noise): float64[n, 3226], row i the Dirichlet(alpha)
+    sample over nvalid[i] valid actions of game env_ids[i] at move moves[i], 0 past nvalid[i]."""
+    # env ids are uint32 in the ABI (the engine takes any 32-bit env_base): through int64, the low 32 bits
+    env = _dev(env_ids, torch.int64).reshape(-1)
+    env = (((env & 0xFFFFFFFF) + 2**31) % 2**32 - 2**31).to(torch.int32).contiguous()
+    n = env.numel()
+    mv = _bcast(moves, n, torch.int32)
+    nv = _bcast(nvalid, n, torch.int32)
+    eta = torch.empty((n, ACTION_SIZE), dtype=torch.float64, device="cuda")
+    call("yk_dirichlet_noise", seed & (2**64 - 1), ptr(env), ptr(mv), ptr(nv), float(alpha), ptr(eta), n,
+         stream_ptr())
+    return eta
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
-           "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "_lib"]
+           "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise", "_lib"]
 
 
 def greedy_action(states):
