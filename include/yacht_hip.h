@@ -271,6 +271,38 @@ int yk_examples_from_records(const void* images, int n_images, int n_envs, int m
 int yk_examples_policies(const void* images, int n_images, int n_envs, int max_moves, int sims, int64_t n_games,
                          int64_t skip, int64_t n_examples, int64_t* pi_indptr, int32_t* pi_cols, double* pi_vals,
                          int64_t nnz_capacity, double* values, int64_t* nnz, void* stream);
+/* Symmetry augmentation of examples, a departure from the reference (whose getSymmetries is the identity),
+ * opt-in: the game depends only on the multisets of the dice and is symmetric in the two auction groups,
+ * while the features and the score actions are positional.  Row i of the call is example k = index_base + i
+ * (a global index into the pooled examples); `flags` is a bit-set of YK_SYM_*; DESIGN.md section 7b-sym.
+ *   Draws: draw d is Philox4x32-10 with counter (d, k & 0xffffffff, epoch_key, 0x40000000) - counter word 3
+ *     is 0 for the game streams and 0x80000000 | move for the root noise - under key (seed lo, seed hi);
+ *     below_d(m) = (x1 * m) >> 32 with x1 the output's word 1 (the game streams' rule).
+ *   A list of length L with first draw b is permuted by perm = [0 .. L-1]; for m = L-1 .. 1:
+ *     j = below_{b + (L-1-m)}(m + 1), swap perm[m], perm[j]; new[i] = old[perm[i]] (an old position p moves
+ *     to perm^-1(p)).  First draws, fixed whatever the flags: p1 carry 0, p2 carry 16, rollA 32, rollB 40;
+ *     the groups are exchanged iff x1 >> 31 of draw 48.
+ *   YK_SYM_CARRY permutes both carries over their own lengths; YK_SYM_ROLLS each roll whose hasA / hasB bit
+ *     is set; YK_SYM_GROUPS, after the rolls, exchanges the rollA / rollB fields and the two has bits and
+ *     XORs 0x80 into each bid byte that is not 0xFF.  Every other bit of the 64 bytes is copied; phase and
+ *     round are not consulted.  A flag that is off leaves its part the identity and moves no draw index.
+ *   Actions (examples are canonical: the mover is p1), a bijection A_k of 0 .. 3225: phase 0 and a < 202:
+ *     (a + 101) mod 202 when the groups were exchanged; phase 1 and 202 <= a, combo positions c0 < .. < c4
+ *     with c4 < len(p1 carry): 202 + cat * 252 + index of sorted(perm1^-1(c)) in COMB_5_OF_10; else a.
+ *   out_states[i] = the board; out_targets[i] = A_k(targets[i]); CSR row i (entries pi_indptr[i] ..
+ *     pi_indptr[i+1]-1 of pi_cols / pi_vals, written at the same positions of out_cols / out_vals): the
+ *     same entries under A_k in ascending new column order, each value with its entry.  pi_indptr is not
+ *     copied.  Columns must lie in 0 .. 3225: another is skipped and its row's output is unspecified.
+ * targets / out_targets may both be NULL, and so may the three CSR inputs with the two CSR outputs; out must
+ * not alias in.  n < 0, flags outside 0 .. 7, a half-given pair, NULL states / out_states with n > 0:
+ * YK_ERR_ARG before anything touches the device.  flags = 0 copies.  Asynchronous on `stream`. */
+#define YK_SYM_CARRY 1
+#define YK_SYM_ROLLS 2
+#define YK_SYM_GROUPS 4
+int yk_examples_augment(const yk_state_t* states, const int32_t* targets, const int64_t* pi_indptr,
+                        const int32_t* pi_cols, const double* pi_vals, int64_t n, int64_t index_base, uint64_t seed,
+                        uint32_t epoch_key, int flags, yk_state_t* out_states, int32_t* out_targets,
+                        int32_t* out_cols, double* out_vals, void* stream);
 
 /* ---------------------------------------------------------------- Arena
  * Batched Arena.playGame (Arena.py:30-93), n_envs games in lock-step: `agent` in seat

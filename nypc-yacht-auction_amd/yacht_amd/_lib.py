@@ -105,13 +105,15 @@ SIGNATURES = {
     "yk_mcts_reset": [P],
     "yk_examples_from_records": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P],
     "yk_examples_policies": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, P, P, P, C.c_int64, P, P, P],
+    "yk_examples_augment": [P, P, P, P, P, C.c_int64, C.c_int64, U64, U32, I, P, P, P, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
-# added in rounds 5-6, with the soft policy targets and with the root noise (A/B baselines may predate them)
+# added in rounds 5-6, with the soft policy targets, the root noise and the symmetry augmentation (A/B
+# baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
-          "yk_engine_root_priors", "yk_dirichlet_noise"}
+          "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment"}
 _lib = None
 
 

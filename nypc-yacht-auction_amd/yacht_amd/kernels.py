@@ -155,8 +155,77 @@ def dirichlet_noise(seed: int, env_ids, moves, nvalid, alpha: float):
     return eta
 
 
+SYMMETRIES = {"carry": 1, "rolls": 2, "groups": 4}  # YK_SYM_CARRY / YK_SYM_ROLLS / YK_SYM_GROUPS
+
+
+def symmetry_flags(symmetries) -> int:
+    """An iterable over {"carry", "rolls", "groups"} -> yk_examples_augment's flags.  An unknown name (or a
+    bare string, which would iterate as letters) raises ValueError; touches no device."""
+    if isinstance(symmetries, str):
+        symmetries = (symmetries,)
+    flags = 0
+    for name in symmetries:
+        if name not in SYMMETRIES:
+            raise ValueError(f"unknown symmetry {name!r}: choose from {sorted(SYMMETRIES)}")
+        flags |= SYMMETRIES[name]
+    return flags
+
+
+def check_policy_columns(policies):
+    """ValueError unless every column of the CSR (pi_indptr, pi_cols, pi_vals) is an action, 0 .. 3225 - what
+    yk_examples_augment requires of its rows.  One device reduction pair; synchronises."""
+    cols = policies[1]
+    if cols.numel():
+        lo, hi = int(cols.min()), int(cols.max())
+        if lo < 0 or hi >= ACTION_SIZE:
+            raise ValueError(f"policy columns must lie in 0 .. {ACTION_SIZE - 1}, found {lo} .. {hi}")
+
+
+def augment_examples(states, targets, policies, seed: int, epoch_key: int, symmetries, index_base: int = 0, out=None):
+    """A random symmetry of every example (yk_examples_augment): row i is example
+    index_base + i of the pool, drawn for (seed, epoch_key).  states int64[n, 8]; targets int32[n] or None;
+    policies the device CSR (pi_indptr, pi_cols, pi_vals) of as_device_policies, the ExampleShard.policies
+    dict, or None; symmetries an iterable over {"carry", "rolls", "groups"} (empty: a copy).  Returns device
+    tensors (states', targets', policies'), policies' sharing pi_indptr with the input; `out` - an earlier
+    return value for inputs of the same sizes - is written instead of new tensors.  Columns must be actions
+    (check_policy_columns); the inputs are not modified."""
+    flags = symmetry_flags(symmetries)
+    st = _dev(states, torch.int64).reshape(-1, 8)
+    n = st.shape[0]
+    tg = None if targets is None else _dev(targets, torch.int32).reshape(n)
+    if isinstance(policies, dict):
+        policies = (policies["pi_indptr"], policies["pi_cols"], policies["pi_vals"])
+    if policies is not None:
+        indptr, cols, vals = policies
+        if indptr.dtype != torch.int64 or cols.dtype != torch.int32 or vals.dtype != torch.float64:
+            raise TypeError("policies: pi_indptr int64, pi_cols int32, pi_vals float64")
+        if indptr.numel() != n + 1:
+            raise ValueError(f"pi_indptr has {indptr.numel()} entries for {n} examples")
+    o_st, o_tg, o_pol = out if out is not None else (None, None, None)
+    if o_st is None:
+        o_st = torch.empty_like(st)
+    if tg is not None and o_tg is None:
+        o_tg = torch.empty_like(tg)
+    if policies is not None and o_pol is None:
+        o_pol = (indptr, torch.empty_like(cols), torch.empty_like(vals))
+    if o_st.shape != st.shape or (tg is not None and o_tg.shape != tg.shape) or \
+            (policies is not None and (o_pol[1].shape != cols.shape or o_pol[2].shape != vals.shape)):
+        raise ValueError("out does not match the inputs' sizes")
+    csr = [None] * 5
+    if policies is not None:
+        # (an empty CSR's cols / vals may have no storage: any non-null pointer does, nothing reads it)
+        csr = [ptr(indptr), ptr(cols) or ptr(indptr), ptr(vals) or ptr(indptr),
+               ptr(o_pol[1]) or ptr(o_st), ptr(o_pol[2]) or ptr(o_st)]
+    call("yk_examples_augment", ptr(st), None if tg is None else ptr(tg), csr[0], csr[1], csr[2], n,
+         int(index_base), seed & (2**64 - 1), int(epoch_key) & 0xFFFFFFFF, flags, ptr(o_st),
+         None if tg is None else ptr(o_tg), csr[3], csr[4], stream_ptr())
+    return o_st, (o_tg if tg is not None else None), \
+        ((indptr, o_pol[1], o_pol[2]) if policies is not None else None)
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
-           "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise", "_lib"]
+           "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
+           "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "_lib"]
 
 
 def greedy_action(states):

@@ -218,16 +218,29 @@ class NNetWrapper:
         args.policy_target: "argmax" (default; the reference's hard label, NNet.py:145-146) or
         "visits" - cross-entropy against the full MCTS visit policy pi = N / sum N (soft targets,
         F.cross_entropy(out_pi, pi); a departure from the reference), in every ddp_batch mode.
-        It needs the policies: tuples, or shards built by examples_from_images."""
+        It needs the policies: tuples, or shards built by examples_from_images.
+
+        args.symmetries: () (default; the reference's getSymmetries is the identity) or an iterable over
+        {"carry", "rolls", "groups"} - symmetry augmentation, a departure from the reference: at the top
+        of every epoch each example (board, target and, for "visits", its policy row) is replaced by a
+        random member of its symmetry class, drawn on the device for (args.seed, the optimiser step count
+        at that moment, the example's index) - K.augment_examples, DESIGN.md 7b-sym - into buffers
+        allocated once per call; the epoch's steps then run unchanged on that copy."""
         from . import dist as D
         from .replay import as_device_examples, as_device_policies
         target = self.args.get("policy_target", "argmax")
         if target not in ("argmax", "visits"):
             raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
+        symmetries = self.args.get("symmetries", ()) or ()
+        symmetries = (symmetries,) if isinstance(symmetries, str) else tuple(symmetries)
+        K.symmetry_flags(symmetries)  # an unknown name: ValueError, before any device work
         tr = self._trainer()
         states, targets, values = as_device_examples(examples)
         # "visits": the same rows' policies as a CSR; "argmax" calls the trainer exactly as before
         soft = {"policies": as_device_policies(examples)} if target == "visits" else {}
+        pool, aug = (states, targets, soft.get("policies")), None
+        if symmetries and soft:
+            K.check_policy_columns(soft["policies"])
         rank, world = D.rank_world()
         n = states.shape[0]
         bs = self.args.batch_size
@@ -239,6 +252,12 @@ class NNetWrapper:
         g = torch.Generator(device="cuda")
         g.manual_seed(int(self.args.get("seed", 0)) + 1000003 * tr.step_count)
         for epoch in range(self.args.epochs):
+            if symmetries and n:  # this epoch's copy of the pool (every rank holds the pool: the same copy)
+                aug = K.augment_examples(*pool, int(self.args.get("seed", 0)), tr.step_count & 0xFFFFFFFF,
+                                         symmetries, out=aug)
+                states, targets = aug[0], aug[1]
+                if soft:
+                    soft = {"policies": aug[2]}
             perm = torch.randperm(n, generator=g, device="cuda").to(torch.int32)
             report = verbose and (epoch % 5 == 0 or epoch == self.args.epochs - 1)
             if report:

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ._lib import call, stream_ptr
+from .kernels import augment_examples  # (a random symmetry of every example; listed with the buffer's functions)
 
 
 def _vcap(max_moves: int, sims: int) -> int:
@@ -208,4 +209,5 @@ def as_device_policies(examples):
     return out if out is not None else as_device_policies([])
 
 
-__all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host"]
+__all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
+           "augment_examples"]
