@@ -179,6 +179,20 @@ typedef struct {
                                actions j (ascending), eta ~ Dir(alpha) = yk_dirichlet_noise(seed, env id, move, V,
                                alpha).  yk_arena and yk_mcts_search never add noise.  The game's draw stream is
                                not consumed.  alpha NaN or < 0, eps outside [0, 1]: YK_ERR_ARG */
+    int record_root_values; /* the search's own value of every real move, a departure from the reference, opt-in
+                               (0 = off: no extra launch, info[..][7] stays 0).  On, yk_selfplay (never yk_arena or
+                               yk_mcts_search) evaluates, after the last simulation of move m of game e, over the
+                               edges (s, a) of the move's root with N > 0 in ascending action order (the
+                               reference's Nsa / Qsa of the root, visits kept from earlier moves included)
+                                   num = 0.0; den = 0.0                                     (float64)
+                                   num = num + (double)N * Q ;  den = den + (double)N       (each edge)
+                                   q32 = (float)(num / den)                                 (nearest even)
+                               every operation rounded on its own (no FMA), N the edge's full count, Q its stored
+                               float64 whatever its Python kind.  info[e][m][7] = the bit pattern of q32, +0 and
+                               -0 both as 0x80000000: a recorded value is never the zero word, and a zero word
+                               means "no value recorded" (flag off, a root not in the tree, den == 0 - the last
+                               two are existing error states - and every move past the game's end).  The search,
+                               the game streams and every other record are unchanged.  DESIGN.md section 7b-val */
 } yk_engine_config_t;
 
 typedef struct yk_engine yk_engine_t;
@@ -196,7 +210,8 @@ int yk_selfplay(yk_engine_t* eng, uint64_t seed, uint32_t env_base, void* stream
  * launches[8] for classes 0 first descent of a move, 1 forward (the whole predict), 2 unused,
  * 3 expand + backup + the next descent, 4 move begin (root / tree compaction), 5 move end
  * (policy, sampling, real step), 6 the root noise (both launches of a move; 0 launches when the noise
- * is off - with it on and full root scans, simulation 1's descent is its own launch, timed as class 2). */
+ * is off - with it on and full root scans, simulation 1's descent is its own launch, timed as class 2),
+ * 7 the root value (one launch per move after the move end; 0 launches without record_root_values). */
 int yk_engine_profile(yk_engine_t* eng, int enable);
 int yk_engine_kernel_times(yk_engine_t* eng, double* ms, int64_t* launches);
 /* HOST out[16]: 0 expansions, 1 valid entries scanned by UCB, 2 real moves (max over games),
@@ -210,7 +225,8 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)
- *   info[n][max_moves][8]    temp, player, action, expansions-so-far, root Ns, n visited, status, 0
+ *   info[n][max_moves][8]    temp, player, action, expansions-so-far, root Ns, n visited, status, 0 (the
+ *                            move's root value word with record_root_values, see yk_engine_config_t)
  *   ctr[n][max_moves][2]     stream counter before the search / before the real step
  *   values[n][max_moves]     example value r*(-1)**(player != curPlayer) (Coach.py:72)
  *   final_states[n][8], n_moves[n]
@@ -271,6 +287,31 @@ int yk_examples_from_records(const void* images, int n_images, int n_envs, int m
 int yk_examples_policies(const void* images, int n_images, int n_envs, int max_moves, int sims, int64_t n_games,
                          int64_t skip, int64_t n_examples, int64_t* pi_indptr, int32_t* pi_cols, double* pi_vals,
                          int64_t nnz_capacity, double* values, int64_t* nnz, void* stream);
+/* Value targets from the search, a departure from the reference (whose example value is the outcome z,
+ * Coach.py:71-72), opt-in: mixes each move's recorded root value into the target (beta) and / or bootstraps
+ * from the later moves' root values, TD(lambda); DESIGN.md section 7b-val.  Images, n_games, skip and the
+ * example numbering are yk_examples_from_records'; examples skip .. skip + n_examples - 1 are written
+ * (n_examples > the examples after skip: YK_ERR_ARG).  The images must come from an engine with
+ * record_root_values unless (beta, lambda) = (0, 1).  Per game with T recorded moves, t = 0 .. T-1:
+ *   p_t = info[t][1] (+1 / -1), z_t = the recorded float64 value, q_t = (double) of the float32 whose bit
+ *   pattern is info[t][7].  All arithmetic float64, every operation rounded on its own (no FMA):
+ *     W_t = p_t * q_t ;  Z_t = p_t * z_t
+ *     G_{T-1} = Z_{T-1} ;  G_t = (1.0 - lambda) * W_{t+1} + lambda * G_{t+1}      t = T-2 .. 0
+ *     target_t = p_t * G_t
+ *     v_t = (1.0 - beta) * target_t + beta * q_t ;  values[k] = (float)v_t       (nearest even, once)
+ *   lambda == 1 skips the recursion: G_t = Z_t for every t, and no later root value is read.  beta == 0 skips
+ *   the q_t term: v_t = target_t.  So (0, 1) is yk_examples_from_records' values bit for bit and needs no
+ *   recorded root value.
+ * DEVICE values[n_examples]; root_values[n_examples] (may be NULL) = q_t as float32, NaN (0x7FC00000) where the
+ * word is 0.  The whole game is read even where skip or n_examples cut it.  A kept example whose formula
+ * needs a root value that is absent (word 0) - its own when beta != 0, any later move's of its game when
+ * lambda != 1 - is counted in HOST *n_missing (may be NULL); when the count is > 0 the call returns
+ * YK_ERR_STATE and the outputs are unspecified.  beta or lambda outside [0, 1] or NaN, n_examples < 0, NULL
+ * values with n_examples > 0, NULL images or a non-positive dimension: YK_ERR_ARG before anything touches the
+ * device.  Synchronises `stream`. */
+int yk_examples_value_targets(const void* images, int n_images, int n_envs, int max_moves, int sims,
+                              int64_t n_games, int64_t skip, int64_t n_examples, double beta, double lambda,
+                              float* values, float* root_values, int64_t* n_missing, void* stream);
 /* Symmetry augmentation of examples, a departure from the reference (whose getSymmetries is the identity),
  * opt-in: the game depends only on the multisets of the dice and is symmetric in the two auction groups,
  * while the features and the score actions are positional.  Row i of the call is example k = index_base + i

@@ -1317,11 +1317,12 @@ struct yk_engine {
     NoiseDev nz{};               // Dirichlet root noise of yk_selfplay (configured: alpha > 0 and eps > 0)
     bool noise = false;
     bool have_priors = false;    // the last batch was a self-play batch with noise: yk_engine_root_priors
+    bool root_values = false;    // record_root_values: k_root_value after each k_move_end of yk_selfplay
 };
 
 namespace {
 // kernel classes for yk_engine_kernel_times
-enum { KC_SELECT = 0, KC_FORWARD = 1, KC_SCAN = 2 /* k_root_sort + the second descent */, KC_EXPAND = 3, KC_MOVE_BEGIN = 4, KC_MOVE_END = 5, KC_NOISE = 6 /* k_root_noise, both phases */, KC_N = 8 };
+enum { KC_SELECT = 0, KC_FORWARD = 1, KC_SCAN = 2 /* k_root_sort + the second descent */, KC_EXPAND = 3, KC_MOVE_BEGIN = 4, KC_MOVE_END = 5, KC_NOISE = 6 /* k_root_noise, both phases */, KC_ROOT_VALUE = 7 /* k_root_value */, KC_N = 8 };
 
 void prof_mark(yk_engine* eng, int g, int cls, hipStream_t s) {  // records an event pair boundary
     if (!eng->prof) return;
@@ -1613,6 +1614,7 @@ constexpr int YK_FPARTS_MAX = 4;
     if (d.prior == 0) {
         A(eng->logits, E * (size_t)PI_LD);
     }
+    eng->root_values = cfg->record_root_values != 0;
     eng->noise = cfg->dirichlet_alpha > 0.0 && cfg->dirichlet_eps > 0.0;
     eng->nz.alpha = cfg->dirichlet_alpha;
     eng->nz.eps = cfg->dirichlet_eps;
@@ -1721,7 +1723,10 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
     YK_HIP(hipMemsetAsync(d.err, 0, sizeof(uint32_t), s));
     YK_HIP(hipMemsetAsync(d.hidx[0], 0, sizeof(uint32_t) * (size_t)d.T * d.HCAP, s));
     const bool noise = eng->noise && !d.arena;  // the arenas never add noise
+    const bool root_values = eng->root_values && !d.arena;  // nor do they record root values
     eng->have_priors = false;
+    if (root_values)  // info[..][7] = 0 also past a game's end: a zero word is "no value recorded"
+        YK_HIP(hipMemsetAsync(d.rec_info, 0, sizeof(int32_t) * (size_t)d.E * d.M * 8, s));
     if (noise && eng->nz.prior_after) {  // dense by action: 0 off the valid set and past the game's end
         const size_t nb = sizeof(float) * (((size_t)d.E + d.rec_stride - 1) / d.rec_stride) * (size_t)d.M * ASIZE;
         YK_HIP(hipMemsetAsync(eng->nz.prior_before, 0, nb, s));
@@ -1748,6 +1753,12 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
             prof_mark(eng, g, KC_MOVE_END, st[g]);
             hipLaunchKernelGGL(k_move_end, game_grid(dg[g]), bb, 0, st[g], dg[g], move);
             YK_LAUNCHED();
+            if (root_values) {  // the games with nmoves == move + 1; root[e] is still this move's root
+                prof_mark(eng, g, KC_ROOT_VALUE, st[g]);
+                const RootValDev rv{move};
+                const int rc = yk_launch_root_value(&dg[g], sizeof(dg[g]), &rv, sizeof(rv), st[g]);
+                if (rc) return rc;
+            }
             prof_mark(eng, g, -1, st[g]);
             if (G > 1) {
                 YK_HIP(hipEventRecord(eng->ev_join[g], st[g]));

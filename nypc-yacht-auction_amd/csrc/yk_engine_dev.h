@@ -1,7 +1,8 @@
 // yk_engine_dev.h - the self-play engine's device-side data layout and tree lookups, shared
-// by yk_engine.hip (the search kernels) and yk_noise.hip (the root-noise kernel).  The root noise is its
-// own translation unit, so the search kernels' code object is the same whether or not the feature is
-// built in.  Internal linkage throughout: each of the two units compiles its own copy.
+// by yk_engine.hip (the search kernels), yk_noise.hip (the root-noise kernel) and yk_rootval.hip (the
+// root-value kernel).  The root noise and the root value are their own translation units, so the search
+// kernels' code object is the same whether or not the features are built in.  Internal linkage
+// throughout: each unit compiles its own copy.
 #pragma once
 #include <math.h>
 
@@ -139,6 +140,11 @@ struct NoiseDev {
     float* prior_after;   // [R][M][3226] and after it (NULL: not recorded)
 };
 
+// The root value of each real move, self-play only: k_root_value's own kernel argument.
+struct RootValDev {
+    int move;             // the move k_move_end has just recorded
+};
+
 enum : uint32_t {
     ERR_NODES = 1u, ERR_EDGES = 2u, ERR_ARENA = 4u, ERR_DEPTH = 8u, ERR_STEP = 16u, ERR_ROUND = 32u,
     ERR_VISITS = 64u, ERR_MOVES = 128u, ERR_ZERO_COUNTS = 256u, ERR_ROOT = 512u, ERR_HASH = 1024u,
@@ -244,8 +250,14 @@ __device__ __forceinline__ int tree_of(const EngDev& d, int e) {
 // compiles its own copy of the structs from this header.  The caller passes its sizeof of each; a unit
 // built against another layout gets YK_ERR_ARG instead of a kernel reading the wrong fields.  Not part
 // of the C ABI: hidden in the shared library.
-static_assert(std::is_trivially_copyable<EngDev>::value && std::is_trivially_copyable<NoiseDev>::value,
-              "EngDev / NoiseDev cross translation units as bytes");
+static_assert(std::is_trivially_copyable<EngDev>::value && std::is_trivially_copyable<NoiseDev>::value &&
+                  std::is_trivially_copyable<RootValDev>::value,
+              "EngDev / NoiseDev / RootValDev cross translation units as bytes");
 __attribute__((visibility("hidden"))) int yk_launch_root_noise(const void* engdev, size_t engdev_bytes,
                                                                const void* noisedev, size_t noisedev_bytes, int move,
                                                                int phase, hipStream_t stream);
+// yk_rootval.hip: launches k_root_value for the games [e_lo, e_hi) of `engdev` after k_move_end(rvdev.move),
+// on the same terms.
+__attribute__((visibility("hidden"))) int yk_launch_root_value(const void* engdev, size_t engdev_bytes,
+                                                               const void* rvdev, size_t rvdev_bytes,
+                                                               hipStream_t stream);

@@ -1,0 +1,116 @@
+// yk_value_targets.hip - value targets from the search: the record images' outcome z
+// and per-move root values q (info[..][7], written by k_root_value with record_root_values) -> the float32
+// value each example is trained on,
+//     G_{T-1} = Z_{T-1} ;  G_t = (1 - lambda) W_{t+1} + lambda G_{t+1} ;  v_t = (1 - beta) p_t G_t + beta q_t
+// in float64 without contraction (-ffp-contract=off), rounded to float32 once.  Its own translation unit:
+// yk_replay.hip's kernels compile as before.  The examples are numbered by yk_replay_dev.h's offsets, as
+// yk_examples_from_records numbers them.
+#include <math.h>
+
+#include "yk_replay_dev.h"
+
+namespace {
+
+__device__ __forceinline__ double lane_f64(double x, int src) {  // x of lane `src` (wave-uniform), to every lane
+    const uint64_t b = (uint64_t)__double_as_longlong(x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, src);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), src);
+    return __longlong_as_double((long long)((uint64_t)lo | ((uint64_t)hi << 32)));
+}
+
+// One wavefront per game.  The game's moves are taken 64 at a time from the last chunk down, lane i move
+// c0 + i; within a chunk the backward recursion runs from the chunk's last move to its first, every lane
+// carrying the same (G_{t+1}, W_{t+1}) in uniform registers and lane i keeping G of its own move - no LDS.
+// The whole game is walked even where skip / cap cut it: a kept move's G depends on the moves after it.
+// Example k = off[g] + m - skip, kept if 0 <= k < cap (as k_examples).  `missing` counts the kept examples
+// whose formula reads a root value that is absent (word 0).
+__global__ void __launch_bounds__(64) k_value_targets(ImgView v, const int64_t* off, int64_t skip, int64_t cap,
+                                                      double beta, double lambda, float* values, float* root_values,
+                                                      unsigned long long* missing) {
+    const int64_t g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int img = (int)(g / v.E), e = (int)(g % v.E);
+    const int64_t base = off[g] - skip;
+    const int n = (int)(off[g + 1] - off[g]);  // <= M
+    const int32_t* info = reinterpret_cast<const int32_t*>(v.part(img, REC_INFO)) + (int64_t)e * v.M * 8;
+    const double* val = reinterpret_cast<const double*>(v.part(img, REC_VALUES)) + (int64_t)e * v.M;
+    const bool td = lambda != 1.0, mix = beta != 0.0;
+    const double keep_l = 1.0 - lambda, keep_b = 1.0 - beta;
+    double G = 0.0, Wn = 0.0;  // G_{t+1}, W_{t+1} of the move last done (wave-uniform)
+    bool absent_later = false;  // a move after t has no root value (wave-uniform)
+    unsigned miss = 0;
+    for (int c0 = n > 0 ? ((n - 1) / 64) * 64 : -1; c0 >= 0; c0 -= 64) {
+        const int m = c0 + lane;
+        const bool in = m < n;
+        const int p_i = in ? info[m * 8 + 1] : 1;
+        const uint32_t word = in ? (uint32_t)info[m * 8 + 7] : 0u;
+        const double z = in ? val[m] : 0.0;
+        const float q32 = word ? __uint_as_float(word) : __uint_as_float(0x7FC00000u);
+        const double p = (double)p_i, q = (double)q32;
+        const double W = p * q, Z = p * z;
+        double Gm = Z;  // lambda == 1: G_t = Z_t
+        bool need_later = false;
+        if (td) {
+            const uint64_t has = __ballot(in && word != 0u);
+            for (int i = min(63, n - 1 - c0); i >= 0; i--) {
+                const int t = c0 + i;
+                const double Wt = lane_f64(W, i);
+                const double Gt = t == n - 1 ? lane_f64(Z, i) : keep_l * Wn + lambda * G;
+                if (lane == i) {
+                    Gm = Gt;
+                    need_later = absent_later;
+                }
+                G = Gt;
+                Wn = Wt;
+                absent_later = absent_later || !((has >> i) & 1ull);
+            }
+        }
+        const int64_t k = base + m;
+        const bool kept = in && k >= 0 && k < cap;
+        if (kept) {
+            const double target = p * Gm;
+            const double vt = mix ? keep_b * target + beta * q : target;
+            values[k] = (float)vt;
+            if (root_values) root_values[k] = q32;
+        }
+        miss += (unsigned)__popcll(__ballot(kept && ((mix && word == 0u) || need_later)));
+    }
+    if (lane == 0 && miss) atomicAdd(missing, (unsigned long long)miss);
+}
+
+}  // namespace
+
+extern "C" int yk_examples_value_targets(const void* images, int n_images, int n_envs, int max_moves, int sims,
+                                         int64_t n_games, int64_t skip, int64_t n_examples, double beta,
+                                         double lambda, float* values, float* root_values, int64_t* n_missing,
+                                         void* stream) {
+    // (a NaN fails both comparisons)
+    if (!(beta >= 0.0 && beta <= 1.0) || !(lambda >= 0.0 && lambda <= 1.0)) return YK_ERR_ARG;
+    if (!images || n_images <= 0 || n_envs <= 0 || max_moves <= 0 || sims < 0 || skip < 0 || n_examples < 0 ||
+        (!values && n_examples > 0))
+        return YK_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    Prep p;
+    const int rc = prepare(images, n_images, n_envs, max_moves, sims, n_games, s, &p);
+    if (rc != YK_OK) return rc;
+    YK_HIP(hipStreamSynchronize(s));
+    if (n_examples > p.total - skip) {  // asks for examples the images do not hold
+        YK_HIP(hipFree(p.off));
+        return YK_ERR_ARG;
+    }
+    unsigned long long* miss = nullptr;
+    unsigned long long host_miss = 0;
+    if (p.n_games > 0 && n_examples > 0) {
+        YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&miss), sizeof(*miss), s));
+        YK_HIP(hipMemsetAsync(miss, 0, sizeof(*miss), s));
+        hipLaunchKernelGGL(k_value_targets, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.off, skip, n_examples,
+                           beta, lambda, values, root_values, miss);
+        YK_LAUNCHED();
+        YK_HIP(hipMemcpyAsync(&host_miss, miss, sizeof(host_miss), hipMemcpyDeviceToHost, s));
+        YK_HIP(hipFreeAsync(miss, s));
+    }
+    YK_HIP(hipFreeAsync(p.off, s));
+    YK_HIP(hipStreamSynchronize(s));
+    if (n_missing) *n_missing = (int64_t)host_miss;
+    return host_miss ? YK_ERR_STATE : YK_OK;
+}

@@ -41,6 +41,14 @@ class YkEngineConfig(C.Structure):
                 ("dirichlet_eps", C.c_double)]
 
 
+class YkEngineConfigFull(YkEngineConfig):
+    """yk_engine_config_t field for field: YkEngineConfig's 80 bytes (the struct up to the root noise, whose
+    layout tests/test_root_noise_host.py pins) and, appended as in the header, the fields added since.
+    This is what SelfPlayEngine passes to yk_engine_create; the bare YkEngineConfig is only good for calls
+    the library rejects before it reads past those 80 bytes."""
+    _fields_ = [("record_root_values", C.c_int)]
+
+
 # name -> argtypes (restype int unless listed in _RESTYPE)
 P = C.c_void_p
 I = C.c_int
@@ -106,14 +114,15 @@ SIGNATURES = {
     "yk_examples_from_records": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P],
     "yk_examples_policies": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, P, P, P, C.c_int64, P, P, P],
     "yk_examples_augment": [P, P, P, P, P, C.c_int64, C.c_int64, U64, U32, I, P, P, P, P, P],
+    "yk_examples_value_targets": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, P, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
-# added in rounds 5-6, with the soft policy targets, the root noise and the symmetry augmentation (A/B
-# baselines may predate them)
+# added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation and the
+# search-value targets (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
-          "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment"}
+          "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets"}
 _lib = None
 
 

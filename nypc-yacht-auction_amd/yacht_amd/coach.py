@@ -63,6 +63,11 @@ log = logging.getLogger(__name__)
 class Coach:
     def __init__(self, game, nnet, args):
         self.game, self.nnet, self.args = game, nnet, args
+        # search-value targets: valueMix = beta, valueLambda = lambda; (0, 1) is off -
+        # the reference's value target, the outcome.  Checked here, before anything touches the device.
+        from .replay import check_value_knobs
+        self.value_mix, self.value_lambda = check_value_knobs(args.get("valueMix", 0.0),
+                                                              args.get("valueLambda", 1.0))
         # the competitor network with the same args (Coach.py:26-27)
         self.pnet = nnet.__class__(game, args) if hasattr(nnet, "train") else None
         self.mcts = MCTS(game, nnet, args)
@@ -85,7 +90,12 @@ class Coach:
                               # root exploration noise of self-play (off unless both are set; the gating
                               # arena and the MCTS plugin never add it)
                               dirichlet_alpha=self.args.get("dirichletAlpha", 0.0),
-                              dirichlet_eps=self.args.get("dirichletEpsilon", 0.0))
+                              dirichlet_eps=self.args.get("dirichletEpsilon", 0.0),
+                              # each move's root value in the records, only when the value targets use it
+                              record_root_values=self._value_targets_on())
+
+    def _value_targets_on(self) -> bool:
+        return (self.value_mix, self.value_lambda) != (0.0, 1.0)
 
     def executeEpisodes(self, n: int):
         """n episodes as the reference's per-game lists of (YachtState, pi, v) (this process only)."""
@@ -114,7 +124,8 @@ class Coach:
         finally:
             eng.close()
         gathered = D.allgather_records(img)
-        return examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen)
+        return examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen,
+                                    value_mix=self.value_mix, value_lambda=self.value_lambda)
 
     # ---- Coach.learn (Coach.py:74-139)
     def learn(self):
@@ -222,4 +233,7 @@ class Coach:
             log.warning(f'File "{examplesFile}" with trainExamples not found!')
             return
         log.info("Loading done!")
+        if self._value_targets_on():  # (a resumed run must still start: the files hold the outcome only)
+            log.warning("valueMix / valueLambda are set, but the examples file holds outcomes only: the "
+                        f"{len(self.trainExamplesHistory)} reloaded iteration(s) train on outcomes")
         self.skipFirstSelfPlay = True  # examples based on the model were already collected

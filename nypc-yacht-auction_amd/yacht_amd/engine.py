@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import YkEngineConfig, call, lib, stream_ptr
+from ._lib import YkEngineConfigFull, call, lib, stream_ptr
 
 ACTION_SIZE = 3226
 
@@ -23,19 +23,23 @@ class SelfPlayEngine:
                  prior: str = "net", max_moves: int = 64, record_predictions: bool = False,
                  max_expansions: int = 0, arena_entries: int = 0, record_stride: int = 1, groups: int = 0,
                  dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
-                 dirichlet_eps: float = 0.0):
+                 dirichlet_eps: float = 0.0, record_root_values: bool = False):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
             raise ValueError("prior='net' needs a YkNet")
-        self.cfg = YkEngineConfig(n_envs=n_envs, sims=sims, cpuct=cpuct, temp_threshold=temp_threshold,
-                                  max_moves=max_moves, prior=0 if prior == "net" else 1,
-                                  record_predictions=int(record_predictions),
-                                  max_expansions=max_expansions or (max_moves * sims + 8),
-                                  arena_entries=arena_entries, record_stride=max(int(record_stride), 1),
-                                  groups=int(groups), dual_trees=int(bool(dual_trees)),
-                                  # AlphaZero's root noise in run() (never in arena()); on when both are > 0
-                                  dirichlet_alpha=float(dirichlet_alpha), dirichlet_eps=float(dirichlet_eps))
+        self.cfg = YkEngineConfigFull(
+            n_envs=n_envs, sims=sims, cpuct=cpuct, temp_threshold=temp_threshold,
+            max_moves=max_moves, prior=0 if prior == "net" else 1,
+            record_predictions=int(record_predictions),
+            max_expansions=max_expansions or (max_moves * sims + 8),
+            arena_entries=arena_entries, record_stride=max(int(record_stride), 1),
+            groups=int(groups), dual_trees=int(bool(dual_trees)),
+            # AlphaZero's root noise in run() (never in arena()); on when both are > 0
+            dirichlet_alpha=float(dirichlet_alpha), dirichlet_eps=float(dirichlet_eps),
+            # the search's own value of each real move of run(), in info[..., 7] (DESIGN.md 7b-val;
+            # never in arena())
+            record_root_values=int(bool(record_root_values)))
         self.net = net  # keep the weights alive
         h = C.c_void_p()
         call("yk_engine_create", C.byref(h), C.byref(self.cfg), C.c_void_p(net.handle if net is not None else None))
@@ -102,6 +106,8 @@ class SelfPlayEngine:
         kt = {k: (float(ms[i]), int(n[i])) for i, k in enumerate(self.KERNEL_CLASSES) if k != "unused"}
         if self.cfg.dirichlet_alpha > 0 and self.cfg.dirichlet_eps > 0:
             kt["root_noise"] = (float(ms[6]), int(n[6]))  # k_root_noise, two launches per move (class 6)
+        if self.cfg.record_root_values:
+            kt["root_value"] = (float(ms[7]), int(n[7]))  # k_root_value, one launch per move (class 7)
         return kt
 
     STAT_NAMES = ("expansions", "scanned", "moves", "errors", "max_nodes", "max_edges", "max_arena", "vnew",
@@ -134,8 +140,11 @@ class SelfPlayEngine:
         call("yk_engine_records", self.handle, states.ctypes.data, info.ctypes.data, ctr.ctypes.data,
              values.ctypes.data, final.ctypes.data, nm.ctypes.data, voff.ctypes.data, visits.ctypes.data,
              nv.ctypes.data)
-        return dict(states=states, info=info, ctr=ctr, values=values, final=final, n_moves=nm,
-                    visits_off=voff.reshape(-1)[:E * M + 1], visits=visits[:int(nv[0])])
+        rec = dict(states=states, info=info, ctr=ctr, values=values, final=final, n_moves=nm,
+                   visits_off=voff.reshape(-1)[:E * M + 1], visits=visits[:int(nv[0])])
+        if self.cfg.record_root_values:
+            rec["root_values"] = decode_root_values(info[:, :, 7])  # float32 [n, max_moves], NaN where absent
+        return rec
 
     def predictions(self, leaves: bool = False):
         """(pi, v, count[, leaves]) of the recorded games (every record_stride-th): pi[r, k] is
@@ -186,6 +195,14 @@ class SelfPlayEngine:
             self.close()
         except Exception:
             pass
+
+
+def decode_root_values(words: np.ndarray) -> np.ndarray:
+    """info[..., 7] words (record_root_values) -> float32 root values: the word is the value's bit pattern
+    (a zero value is stored as 0x80000000, so it comes back as -0.0), and the zero word - no value
+    recorded - becomes NaN."""
+    w = np.ascontiguousarray(words, dtype=np.int32).view(np.uint32)
+    return np.where(w == 0, np.uint32(0x7FC00000), w).astype(np.uint32).view(np.float32)
 
 
 def unpack_record_image(buf: np.ndarray, n_envs: int, max_moves: int, sims: int) -> dict:

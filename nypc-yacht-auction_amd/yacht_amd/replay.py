@@ -18,7 +18,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from ._lib import call, stream_ptr
+from ._lib import YK_ERR_STATE, YK_OK, YkError, call, lib, stream_ptr
 from .kernels import augment_examples  # (a random symmetry of every example; listed with the buffer's functions)
 
 
@@ -32,11 +32,18 @@ class ExampleShard:
     ``values`` float32[n], and - when built from record images - ``policies``: the full visit
     policies as a device CSR (``pi_indptr`` int64[n+1], ``pi_cols`` int32, ``pi_vals`` float64,
     ``values64`` float64[n]; yk_examples_policies).  ``len`` and iteration behave like the
-    reference's deque of ``(YachtState, pi list, v)`` tuples."""
+    reference's deque of ``(YachtState, pi list, v)`` tuples.
 
-    def __init__(self, states, targets, values, policies=None):
+    ``values`` is what NNetWrapper.train fits the value head to.  By default it is the outcome z; built
+    with ``value_mix`` / ``value_lambda`` it is the search-value target, and the shard
+    also carries ``outcomes`` (z, float32) and ``root_values`` (each move's root value, float32).  The
+    tuples, ``policies["values64"]`` and the examples files keep the reference's v, the outcome."""
+
+    def __init__(self, states, targets, values, policies=None, outcomes=None, root_values=None):
         self.states, self.targets, self.values = states, targets, values
         self.policies = policies
+        self.outcomes = values if outcomes is None else outcomes
+        self.root_values = root_values
         self._host = None
 
     def __len__(self):
@@ -76,12 +83,29 @@ class ExampleShard:
         return unpack(h["states"][k]), pi, float(h["values"][k])
 
 
+def check_value_knobs(value_mix, value_lambda):
+    """(beta, lambda) of the search-value targets as floats; ValueError unless both lie in [0, 1]."""
+    beta, lam = float(value_mix), float(value_lambda)
+    if not 0.0 <= beta <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"value_mix must lie in [0, 1], got {value_mix!r}")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"value_lambda must lie in [0, 1], got {value_lambda!r}")
+    return beta, lam
+
+
 def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims: int, n_games: int = -1,
-                         maxlen: int = None, stream=None) -> ExampleShard:
+                         maxlen: int = None, stream=None, value_mix: float = 0.0,
+                         value_lambda: float = 1.0) -> ExampleShard:
     """Record images (device uint8 [R, nbytes]: every rank's yk_engine_pack_records after the
     all-gather) -> ExampleShard of the first n_games games, keeping the last `maxlen` examples
     (the maxlenOfQueue deque, Coach.py:86-90).  The shard holds only compact arrays (examples and
-    the policies' CSR, about a third of the images' bytes); the images can be released."""
+    the policies' CSR, about a third of the images' bytes); the images can be released.
+
+    value_mix (beta) and value_lambda (lambda), off at (0, 1): the shard's ``values`` become the
+    search-value targets of yk_examples_value_targets - the outcome bootstrapped from the later moves' root
+    values (lambda < 1) and mixed with the move's own (beta > 0); the images must then come from engines
+    created with record_root_values.  ``outcomes`` and the tuples keep z."""
+    beta, lam = check_value_knobs(value_mix, value_lambda)
     imgs = images.reshape(images.shape[0] if images.dim() > 1 else 1, -1).contiguous()
     R = imgs.shape[0]
     cnt = C.c_int64()
@@ -109,7 +133,19 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
     call("yk_examples_policies", imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, indptr.data_ptr(),
          cols.data_ptr(), vals.data_ptr(), k, v64.data_ptr(), C.byref(nnz), sp)
     pol = dict(pi_indptr=indptr, pi_cols=cols[:k], pi_vals=vals[:k], values64=v64[:n])
-    return ExampleShard(states[:n], targets[:n], values[:n], policies=pol)
+    if (beta, lam) == (0.0, 1.0):
+        return ExampleShard(states[:n], targets[:n], values[:n], policies=pol)
+    tgt = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
+    rootv = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
+    missing = C.c_int64()
+    rc = lib().yk_examples_value_targets(imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, beta, lam,
+                                         tgt.data_ptr(), rootv.data_ptr(), C.byref(missing), sp)
+    if rc == YK_ERR_STATE and missing.value > 0:
+        raise ValueError(f"{missing.value} of {n} examples need a root value the record images do not hold: "
+                         "value_mix / value_lambda need engines created with record_root_values=True")
+    if rc != YK_OK:
+        raise YkError("yk_examples_value_targets", rc)
+    return ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n], root_values=rootv[:n])
 
 
 # ---------------------------------------------------------------- what NNetWrapper.train takes
