@@ -151,6 +151,47 @@ int yk_net_errors(yk_net_t* net, uint32_t* flags);
 #define YK_PREDICT_F16 1
 int yk_net_set_precision(yk_net_t* net, int mode);
 
+/* ---------------------------------------------------------------- held-out evaluation
+ * A forward without dropout and, over its raw logits, YK_EVAL_COLS float64 numbers per example.  Not in the
+ * reference; opt-in (Coach args.holdoutEps, python -m yacht_amd.evaluate).
+ *
+ * The raw pi_head output: DEVICE logits[n][3264] (columns >= 3226 unspecified) and v[n] = tanh(v_head), in
+ * the net's current precision mode; exp(log_softmax(logits[i][:3226])) is yk_net_predict's pi.
+ * Asynchronous on `stream`. */
+int yk_net_logits(yk_net_t* net, const yk_state_t* states, float* logits, float* v, int n, void* stream);
+/* The metrics over logits the caller supplies (DEVICE logits[n][ld], ld >= 3226, and v[n]).  Row i belongs to
+ * example r = batch_idx[i] (i when batch_idx is NULL); DEVICE states (canonical boards), targets, values
+ * and the policy CSR (pi_indptr[.. + 1], pi_cols, pi_vals float64; all three or all NULL) are indexed by r.
+ * With x the row's 3226 logits, t = targets[r], z = values[r], (c_k, p_k) the CSR row, all arithmetic float64
+ * (x, v, z widened from float32, every operation rounded on its own), rows[i][0..15] =
+ *    0 lse = m + log(s), m = max x, e_a = exp(x_a - m), s = sum e_a
+ *    1 lse - x_t, the hard cross-entropy (0 when t is outside 0..3225)
+ *    2 the target's rank: #{a : x_a > x_t, or x_a == x_t and a < t} (3226 when t is outside)
+ *    3 the policy's entropy lse - (sum e_a x_a) / s
+ *    4 the policy's mass on getValidMoves(state r, 1): (sum over valid a of e_a) / s
+ *    5 S = sum p_k          6 the soft cross-entropy sum p_k (lse - x[c_k]) over the entries with 0 <= c_k < 3226
+ *    7 the target's entropy -sum over p_k > 0 of p_k log p_k               (5 - 7: 0 without a CSR)
+ *    8 v    9 d = v - z    10 d * d    11 1.0 when v * z > 0    12 1.0 when col 2 == 0    13 1.0 when col 2 < 5
+ *    14 1.0 when t is outside 0..3225    15 1.0
+ * NaN or infinite logits propagate into the row.  HOST sums[16] = the column sums in an order fixed by n:
+ * partial j (0..255) of a column is the sequential sum, from 0.0, of rows j, j + 256, j + 512, ... ascending, and
+ * the sum is the sequential sum, from 0.0, of partials 0..255 ascending - so equal inputs give equal bits.
+ * DEVICE rows[n][16] may be NULL (only the sums are wanted; a temporary is used).  Synchronises `stream`.
+ * NULL required pointers, n < 0, ld < 3226, a half-given CSR: YK_ERR_ARG before any device work; n == 0: YK_OK
+ * with sums all zero. */
+#define YK_EVAL_COLS 16
+int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const yk_state_t* states,
+                        const int32_t* targets, const float* values, const int64_t* pi_indptr,
+                        const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
+                        double* rows, double* sums, void* stream);
+/* yk_net_logits + yk_examples_metrics over examples batch_idx[0 .. n-1] (0 .. n-1 when NULL), `chunk` rows at
+ * a time (<= 0: 16384, about 214 MB of logits scratch, allocated once per call on `stream`); one reduction
+ * over all n rows at the end.  rows and sums do not depend on chunk.  Arguments, errors and synchronisation as
+ * yk_examples_metrics. */
+int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                    const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                    const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream);
+
 /* ---------------------------------------------------------------- self-play engine
  * Batched Coach.executeEpisode (Coach.py:34-72) over n_envs games in lock-step; every game
  * runs MCTS.getActionProb (MCTS.py:28-54) / MCTS.search (MCTS.py:56-164) with its own

@@ -115,14 +115,18 @@ SIGNATURES = {
     "yk_examples_policies": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, P, P, P, C.c_int64, P, P, P],
     "yk_examples_augment": [P, P, P, P, P, C.c_int64, C.c_int64, U64, U32, I, P, P, P, P, P],
     "yk_examples_value_targets": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, P, P, P],
+    "yk_net_logits": [P, P, P, P, I, P],
+    "yk_examples_metrics": [P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int64, P, P, P],
+    "yk_net_evaluate": [P, P, P, P, P, P, P, P, C.c_int64, I, P, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
-# added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation and the
-# search-value targets (A/B baselines may predate them)
+# added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
+# search-value targets and the held-out evaluation (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
-          "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets"}
+          "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
+          "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate"}
 _lib = None
 
 

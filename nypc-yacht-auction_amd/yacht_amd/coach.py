@@ -12,6 +12,9 @@ any number of ranks (one process per GPU, torch.distributed):
   an all-reduce of the gradients (DDP), so every rank holds the same new net;
 * gating: ``arena.GatingArena`` - pmcts vs nmcts as one dual-tree device batch, games sharded,
   tallies summed - then accept / reject as Coach.py:127-139.
+* held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
+  iteration that never enter training, on which the previous and the new net are evaluated after
+  train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
 
 Randomness comes from per-game Philox streams ``(game seed, env id)``: the Coach hands out
 consecutive env ids starting at the game's own (``_streams``), episodes first, then each
@@ -68,6 +71,13 @@ class Coach:
         from .replay import check_value_knobs
         self.value_mix, self.value_lambda = check_value_knobs(args.get("valueMix", 0.0),
                                                               args.get("valueLambda", 1.0))
+        # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
+        self.holdout_eps = int(args.get("holdoutEps", 0) or 0)
+        if self.holdout_eps < 0:
+            raise ValueError(f"holdoutEps must be >= 0, got {args.get('holdoutEps')!r}")
+        self.holdoutHistory = []  # one ExampleShard per iteration, the trainExamplesHistory window
+        self.last_eval = None     # {"prev": ..., "new": ...} of the last iteration (NNetWrapper.evaluate's dicts)
+        self.eval_history = []
         # the competitor network with the same args (Coach.py:26-27)
         self.pnet = nnet.__class__(game, args) if hasattr(nnet, "train") else None
         self.mcts = MCTS(game, nnet, args)
@@ -152,6 +162,10 @@ class Coach:
             if not self.skipFirstSelfPlay or i > 1:
                 self.trainExamplesHistory.append(self.selfPlayExamples(a.numEps, maxlen=a.maxlenOfQueue))
             t["selfplay"] = clock()
+            if self.holdout_eps:  # its own consecutive streams, right after the iteration's self-play games
+                self.holdoutHistory.append(self.selfPlayExamples(self.holdout_eps))
+                del self.holdoutHistory[:-a.numItersForTrainExamplesHistory]
+                t["holdout"] = clock()
             if len(self.trainExamplesHistory) > a.numItersForTrainExamplesHistory:
                 log.warning(f"Removing the oldest entry in trainExamples. len(trainExamplesHistory) = "
                             f"{len(self.trainExamplesHistory)}")
@@ -167,6 +181,16 @@ class Coach:
             # that reshuffle
             self.nnet.train(self.trainExamplesHistory)
             t["train"] = clock()
+            if self.holdout_eps:  # every rank: the ranks hold the same nets and the same pooled games
+                self.last_eval = {"prev": self.pnet.evaluate(self.holdoutHistory),
+                                  "new": self.nnet.evaluate(self.holdoutHistory)}
+                self.eval_history.append(self.last_eval)
+                pe, ne = self.last_eval["prev"], self.last_eval["new"]
+                log.info("HELD-OUT %d examples, PREV / NEW : loss %.4f / %.4f ; policy_ce %.4f / %.4f ; top1 %.4f / "
+                         "%.4f ; value_mse %.4f / %.4f" % (ne["n"], pe["loss"], ne["loss"], pe["policy_ce"],
+                                                          ne["policy_ce"], pe["top1"], ne["top1"], pe["value_mse"],
+                                                          ne["value_mse"]))
+                t["eval"] = clock()
             log.info("PITTING AGAINST PREVIOUS VERSION")
             pwins, nwins, draws = GatingArena(self.game, self.pnet, self.nnet, a).playGames(
                 a.arenaCompare, env_base=self._streams(2 * int(a.arenaCompare / 2)))
@@ -184,8 +208,10 @@ class Coach:
             self.last_pit = (pwins, nwins, draws)
             D.barrier()
             t["gate"] = clock()
-            keys = ["t0", "selfplay", "save", "train", "arena", "gate"]
+            keys = [k for k in ("t0", "selfplay", "holdout", "save", "train", "eval", "arena", "gate") if k in t]
             self.phase_times = {k + "_s": t[k] - t[p] for p, k in zip(keys, keys[1:])}
+            if self.holdout_eps:  # eval_s: everything the held-out evaluation adds, its games included
+                self.phase_times["eval_s"] += self.phase_times.pop("holdout_s")
             self.phase_times["iteration_s"] = t["gate"] - t["t0"]
         self.wait_saves()
 
@@ -236,4 +262,7 @@ class Coach:
         if self._value_targets_on():  # (a resumed run must still start: the files hold the outcome only)
             log.warning("valueMix / valueLambda are set, but the examples file holds outcomes only: the "
                         f"{len(self.trainExamplesHistory)} reloaded iteration(s) train on outcomes")
+        if self.holdout_eps:  # (the files hold the training games only)
+            log.info("holdoutEps is set: the held-out games are not stored in the examples file, the held-out "
+                     "window starts empty")
         self.skipFirstSelfPlay = True  # examples based on the model were already collected

@@ -4,7 +4,8 @@
 ``state_dict`` names and initialisation match; torch only holds the weights.  Inference
 (``NNetWrapper.predict``, NNet.py:177-195) runs through ``yk_net_predict`` - featurize,
 13 dense layers, both heads and exp(log_softmax) on the GPU; ``NNetWrapper.train``
-(NNet.py:118-174) through the native trainer (train.py, yk_trainer_*).
+(NNet.py:118-174) through the native trainer (train.py, yk_trainer_*); ``NNetWrapper.evaluate`` (not in
+the reference: a forward without dropout and float64 metrics over its logits) through ``yk_net_evaluate``.
 """
 from __future__ import annotations
 
@@ -69,6 +70,54 @@ class YachtNNet(nn.Module):  # YachtNNet.py:24-70
 
 
 PRECISIONS = {"f32": 0, "f16": 1}  # YK_PREDICT_F32 / YK_PREDICT_F16 (include/yacht_hip.h)
+PI_LD = 3264    # row stride of the raw logits (yk_net_logits): 3226 padded to 204 tiles of 16 columns
+EVAL_COLS = 16  # YK_EVAL_COLS: the per-example columns of yk_examples_metrics / yk_net_evaluate
+
+
+def check_eval_args(states, targets, values, policies, idx, chunk):
+    """The shapes and dtypes YkNet.evaluate takes, checked before anything touches the device
+    (ValueError); returns the policies' CSR as a 3-tuple with non-empty arrays, or None."""
+    N = states.shape[0]
+    if states.dtype != torch.int64 or states.dim() != 2 or states.shape[1] != 8:
+        raise ValueError("states must be int64[N, 8] (packed boards)")
+    if targets.dtype != torch.int32 or tuple(targets.shape) != (N,):
+        raise ValueError("targets must be int32[N]")
+    if values.dtype != torch.float32 or tuple(values.shape) != (N,):
+        raise ValueError("values must be float32[N]")
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1):
+        raise ValueError("idx must be int32[n]")
+    if int(chunk) != chunk or chunk >= 2 ** 31:
+        raise ValueError(f"chunk must be an int (0: the default), got {chunk!r}")
+    if policies is None:
+        return None
+    if len(policies) != 3:
+        raise ValueError("policies must be (pi_indptr, pi_cols, pi_vals)")
+    indptr, cols, vals = policies
+    if indptr.dtype != torch.int64 or tuple(indptr.shape) != (N + 1,):
+        raise ValueError("pi_indptr must be int64[N + 1]")
+    if cols.dtype != torch.int32 or vals.dtype != torch.float64 or cols.shape != vals.shape or cols.dim() != 1:
+        raise ValueError("pi_cols must be int32[nnz] and pi_vals float64[nnz]")
+    if cols.numel() == 0:  # (no entries at all: the call still wants three pointers)
+        cols, vals = cols.new_zeros(1), vals.new_zeros(1)
+    return indptr, cols, vals
+
+
+def eval_summary(sums, soft: bool) -> dict:
+    """The 16 column sums of yk_net_evaluate (include/yacht_hip.h) -> plain numbers: every mean is
+    sums[c] / n (NaN when n == 0); policy_kl = (soft cross-entropy - target entropy) / the rows' total
+    target mass.  The three soft entries are None when no policies were given."""
+    s = [float(x) for x in sums]
+    n = int(s[15])
+    nan = float("nan")
+
+    def mean(c):
+        return s[c] / n if n else nan
+    out = dict(n=n, bad_targets=int(s[14]), policy_ce=mean(1), top1=mean(12), top5=mean(13), policy_entropy=mean(3),
+               valid_mass=mean(4), policy_ce_soft=None, target_entropy=None, policy_kl=None,
+               value_mse=mean(10), value_bias=mean(9), value_sign_acc=mean(11))
+    if soft:
+        out.update(policy_ce_soft=mean(6), target_entropy=mean(7), policy_kl=(s[6] - s[7]) / s[5] if s[5] else nan)
+    return out
 
 
 class YkNet:
@@ -129,6 +178,36 @@ class YkNet:
              stream_ptr())
         return actions, probs
 
+    def logits(self, states: torch.Tensor):
+        """states int64[n, 8] (device) -> (logits f32[n, 3264], v f32[n]): the raw pi_head output
+        (yk_net_logits; columns >= 3226 are padding) and the value, in this net's precision mode."""
+        n = states.shape[0]
+        logits = torch.empty((n, PI_LD), dtype=torch.float32, device="cuda")
+        v = torch.empty(n, dtype=torch.float32, device="cuda")
+        if n:
+            call("yk_net_logits", self.handle, ptr(states.contiguous()), ptr(logits), ptr(v), n, stream_ptr())
+        return logits, v
+
+    def evaluate(self, states, targets, values, policies=None, idx=None, chunk=0, per_row=False) -> dict:
+        """Forward-only, dropout-free metrics of this net on examples (yk_net_evaluate):
+        device states int64[N, 8], targets int32[N], values f32[N], optionally the policies' CSR
+        (pi_indptr int64[N + 1], pi_cols int32, pi_vals float64) and idx int32[n], the examples to take
+        (all N when None).  Returns eval_summary of the column sums; per_row adds ``rows``, the device
+        float64 [n, 16] columns.  `chunk` rows per forward (0: 16384) - the result does not depend on it."""
+        csr = check_eval_args(states, targets, values, policies, idx, chunk)
+        n = int(idx.numel()) if idx is not None else int(states.shape[0])
+        rows = torch.empty((n, EVAL_COLS), dtype=torch.float64, device="cuda") if per_row else None
+        sums = (C.c_double * EVAL_COLS)()
+        if n:
+            call("yk_net_evaluate", self.handle, ptr(states), ptr(targets), ptr(values),
+                 *([ptr(t) for t in csr] if csr else [None, None, None]),
+                 ptr(idx) if idx is not None else None, n, int(chunk), ptr(rows) if per_row else None, sums,
+                 stream_ptr())
+        out = eval_summary(sums, soft=csr is not None)
+        if per_row:
+            out["rows"] = rows
+        return out
+
     def errors(self) -> int:
         """The device check flags of this net's forwards since the last call (yk_net_errors; synchronises
         the device): 0, or YK_NET_ERR_SYNC when a value-head wave timed out on its v_head.2 hand-off."""
@@ -175,6 +254,35 @@ class NNetWrapper:
 
     def predict_batch(self, states: torch.Tensor):
         return self.yk_net().predict_states(states)
+
+    # ---- held-out evaluation (not in the reference)
+    def eval_target(self, target=None) -> str:
+        target = self.args.get("policy_target", "argmax") if target is None else target
+        if target not in ("argmax", "visits"):
+            raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
+        return target
+
+    def evaluate(self, examples, target=None) -> dict:
+        """Forward only, dropout off: YkNet.evaluate's numbers for this net on `examples` - every form
+        train takes (tuples, an ExampleShard, a list of either).  The values are always the outcome
+        (a shard's ``outcomes``, never its knob-dependent ``values``), so runs with different valueMix /
+        valueLambda stay comparable.  Adds ``loss`` = policy term + vloss_weight * value_mse, the policy
+        term being policy_ce, or policy_ce_soft when `target` (default args.policy_target) is "visits" -
+        which needs the policies, as train does; with "argmax" the soft entries are None when the
+        examples carry no policies."""
+        from .replay import as_device_examples, as_device_policies
+        target = self.eval_target(target)
+        states, targets, values = as_device_examples(examples, outcomes=True)
+        try:
+            policies = as_device_policies(examples)
+        except ValueError:
+            if target == "visits":
+                raise
+            policies = None
+        out = self.yk_net().evaluate(states, targets, values, policies=policies)
+        term = out["policy_ce_soft"] if target == "visits" else out["policy_ce"]
+        out["loss"] = term + float(self.args.get("vloss_weight", 1.0)) * out["value_mse"]
+        return out
 
     # ---- training (NNet.py:118-174) on the native trainer (yacht_amd/train.py)
     def uses_amp(self) -> bool:

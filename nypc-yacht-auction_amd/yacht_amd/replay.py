@@ -153,19 +153,21 @@ def _is_example(x) -> bool:
     return isinstance(x, tuple) and len(x) == 3 and not isinstance(x[0], (ExampleShard, list, deque))
 
 
-def as_device_examples(examples):
+def as_device_examples(examples, outcomes=False):
     """examples: an ExampleShard, a list of (board, pi, v) tuples (Coach.py:72), or a list of
-    either (trainExamplesHistory) -> device (states int64[n, 8], targets int32[n], values f32[n])."""
+    either (trainExamplesHistory) -> device (states int64[n, 8], targets int32[n], values f32[n]).
+    outcomes: a shard gives its ``outcomes`` (z) instead of its ``values`` (the training target, which
+    the value knobs may have changed) - what NNetWrapper.evaluate measures against; tuples carry z anyway."""
     from .train import examples_to_device
     if isinstance(examples, ExampleShard):
-        return examples.states, examples.targets, examples.values
+        return examples.states, examples.targets, examples.outcomes if outcomes else examples.values
     items = list(examples)
     if not items or _is_example(items[0]):
         if not items:
             return (torch.zeros((0, 8), dtype=torch.int64, device="cuda"),
                     torch.zeros(0, dtype=torch.int32, device="cuda"), torch.zeros(0, dtype=torch.float32, device="cuda"))
         return examples_to_device(items)
-    parts = [as_device_examples(x) for x in items]
+    parts = [as_device_examples(x, outcomes) for x in items]
     parts = [p for p in parts if p[1].numel()]
     if not parts:
         return as_device_examples([])
