@@ -46,7 +46,9 @@ typedef struct { uint64_t w[8]; } yk_state_t;
 #define YK_ERR_NOMEM (-3)
 #define YK_ERR_CAPACITY (-4) /* a fixed-size engine pool overflowed; results invalid */
 #define YK_ERR_STATE (-5)    /* engine misuse (e.g. MCTS root round went backwards) */
-#define YK_ERR_RANGE (-6)    /* a weight outside the fp16 split's range (|w| >= 65520: its hi plane overflows) */
+#define YK_ERR_RANGE (-6)    /* a value outside the range an operation accepts: a net weight outside the fp16
+                                split's (|w| >= 65520: its hi plane overflows); a sampling weight that is negative
+                                or NaN, or weights whose total is not finite and > 0 (yk_sample_cdf) */
 
 /* per-element status of yk_step: the reference's exceptions */
 #define YK_ST_OK 0
@@ -191,6 +193,43 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
 int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
                     const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
                     const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream);
+
+/* ---------------------------------------------------------------- weighted minibatch sampling
+ * Which examples a train step sees, drawn with replacement from per-example weights: recency x policy
+ * surprise.  Not in the reference; opt-in (NNetWrapper args.trainSteps / sampleRecency / sampleSurprise).
+ * All arithmetic is float64, every operation rounded on its own in the order written here; no atomics; equal
+ * inputs give equal bits.  n <= 2^31 - 1.
+ *
+ * The weights.  DEVICE rows[n][ld], ld >= 16, is yk_net_evaluate's per-row table (NULL allowed only when
+ * surprise == 0); HOST seg_ptr[nseg + 1] (seg_ptr[0] = 0, seg_ptr[nseg] = n, nondecreasing: empty segments
+ * allowed) and HOST seg_factor[nseg] (finite, >= 0) give every example its segment's factor; 1 <= nseg <= 64;
+ * surprise = sigma in [0, 1].  Per example i, with S, c, h = rows[i][5], [6], [7]: k_i = max(0, (c - h) / S)
+ * when S > 0 and the quotient is finite, else 0 (a negative KL from rounding, a NaN row and a row without a
+ * policy are "no surprise", not errors).  K = the sum of the k_i in yk_examples_metrics' order (partial j of
+ * 256 = the sequential sum from 0.0 of rows j, j + 256, ... ascending; K = the sequential sum from 0.0 of
+ * partials 0..255), written to HOST *ksum (0 when rows is NULL).  s_i = 1.0 when surprise == 0 or K == 0,
+ * else a = (double)n * k_i; b = a / K; c2 = surprise * b; s_i = (1.0 - surprise) + c2.  DEVICE
+ * w[i] = seg_factor[segment of i] * s_i.  Synchronises `stream`. */
+int yk_sample_weights(const double* rows, int64_t ld, const int64_t* seg_ptr, const double* seg_factor, int nseg,
+                      double surprise, int64_t n, double* w, double* ksum, void* stream);
+/* The cumulative distribution of DEVICE w[n] into DEVICE cdf[n] (not aliasing w), in an order fixed by n alone:
+ * chunk c is elements 256 c .. min(256 c + 255, n - 1); L[i] = the sequential inclusive sum of i's chunk from
+ * 0.0, ascending; O[0] = 0.0, O[c + 1] = O[c] + L[last element of c], sequentially; cdf[i] = O[c] + L[i];
+ * HOST *total = cdf[n - 1].  cdf[last of c] is O[c + 1] exactly, so cdf is nondecreasing.  YK_ERR_RANGE when a
+ * weight is negative or NaN, or the total is not finite and > 0 (cdf is then unspecified).  Synchronises. */
+int yk_sample_cdf(const double* w, int64_t n, double* cdf, double* total, void* stream);
+/* m draws located in DEVICE cdf[n] (nondecreasing, as yk_sample_cdf leaves it) into DEVICE idx[m]: draw
+ * j = first + r, r = 0 .. m-1, is Philox4x32-10 with counter (j lo, j hi, key, 0x20000000) - counter word 3 is 0
+ * for the game streams, 0x40000000 for the symmetries and 0x80000000 | move for the root noise - under key
+ * (seed lo, seed hi); x = x0 | x1 << 32, u = (x >> 11) * 2^-53 (the game streams' uniform); t = u * cdf[n - 1];
+ * idx[r] = #{i : cdf[i] <= t} (numpy's searchsorted(cdf, t, 'right')), and where that is n (u * total can round
+ * up to the total) the first i with cdf[i] >= cdf[n - 1].  An element whose weight is zero, or absorbed by
+ * the running sum, is never drawn.  m == 0: YK_OK, nothing launched.  Asynchronous on `stream`.
+ * All three: NULL pointers, n <= 0 or > 2^31 - 1, m < 0, ld < 16, seg_ptr not as above, a factor negative or
+ * not finite, nseg outside 1..64, surprise outside [0, 1] or NaN: YK_ERR_ARG before anything touches the
+ * device. */
+int yk_sample_draw(const double* cdf, int64_t n, uint64_t seed, uint32_t key, uint64_t first, int64_t m, int32_t* idx,
+                   void* stream);
 
 /* ---------------------------------------------------------------- self-play engine
  * Batched Coach.executeEpisode (Coach.py:34-72) over n_envs games in lock-step; every game

@@ -71,6 +71,10 @@ class Coach:
         from .replay import check_value_knobs
         self.value_mix, self.value_lambda = check_value_knobs(args.get("valueMix", 0.0),
                                                               args.get("valueLambda", 1.0))
+        # weighted minibatch sampling: NNetWrapper.train's knobs, checked here as well
+        from .replay import check_sample_knobs
+        check_sample_knobs(args.get("trainSteps", 0) or 0, args.get("sampleRecency", 1.0),
+                           args.get("sampleSurprise", 0.0))
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
         self.holdout_eps = int(args.get("holdoutEps", 0) or 0)
         if self.holdout_eps < 0:

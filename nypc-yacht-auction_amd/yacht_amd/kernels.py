@@ -223,9 +223,74 @@ def augment_examples(states, targets, policies, seed: int, epoch_key: int, symme
         ((indptr, o_pol[1], o_pol[2]) if policies is not None else None)
 
 
+# ---------------------------------------------------------------- weighted minibatch sampling
+def sample_weights(rows, seg_lens, seg_factors, surprise: float):
+    """Per-example sampling weights (yk_sample_weights): w[i] = seg_factors[segment of i] * s_i over the
+    sum(seg_lens) pooled examples, segment s being the next seg_lens[s] of them (zeros allowed; 1 to 64
+    segments, factors finite and >= 0).  rows: YkNet.evaluate(..., per_row=True)'s device float64 [n, >= 16]
+    table, or None when surprise is 0 (then s_i = 1).  Returns (w float64[n] on the device, K) with K the
+    summed policy KL the surprise term is normalised by.  Synchronises."""
+    import ctypes as C
+    lens = [int(x) for x in seg_lens]
+    fac = [float(x) for x in seg_factors]
+    if len(lens) != len(fac):
+        raise ValueError(f"{len(lens)} segment lengths for {len(fac)} factors")
+    n, nseg = sum(lens), len(lens)
+    ld = 0
+    if rows is not None:
+        if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[0] != n:
+            raise ValueError(f"rows must be float64[{n}, >= 16]")
+        ld = int(rows.shape[1])
+    seg_ptr = (C.c_int64 * (nseg + 1))(*np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).tolist())
+    seg_fac = (C.c_double * max(nseg, 1))(*fac)
+    w = torch.empty(max(n, 0), dtype=torch.float64, device="cuda")
+    ksum = C.c_double()
+    call("yk_sample_weights", None if rows is None else ptr(rows), ld, seg_ptr, seg_fac, nseg, float(surprise), n,
+         ptr(w) if n > 0 else None, C.byref(ksum), stream_ptr())
+    return w, float(ksum.value)
+
+
+def sample_cdf(w):
+    """The cumulative distribution of device float64 weights (yk_sample_cdf), nondecreasing, in an order fixed
+    by their number: (cdf float64[n], total = cdf[-1]).  ValueError when a weight is negative or NaN or the
+    total is not finite and positive.  Synchronises."""
+    import ctypes as C
+    if w.dtype != torch.float64 or w.dim() != 1:
+        raise ValueError("w must be float64[n]")
+    n = int(w.numel())
+    cdf = torch.empty_like(w)
+    total = C.c_double()
+    try:
+        call("yk_sample_cdf", ptr(w) if n else None, n, ptr(cdf) if n else None, C.byref(total), stream_ptr())
+    except _lib.YkError as e:
+        if e.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError("sampling weights must be >= 0 with a finite, positive total") from None
+    return cdf, float(total.value)
+
+
+def sample_draw(cdf, seed: int, key: int, first: int, m: int, out=None):
+    """m draws with replacement from the distribution of sample_cdf's table (yk_sample_draw): int32[m] device
+    indices, draw r being draw first + r of the stream (seed, key) - equal calls give equal indices, and a
+    range of draws is that range of a longer call.  `out`: an int32 device tensor of at least m elements to
+    write into (its first m are returned).  Asynchronous on the current stream."""
+    if cdf.dtype != torch.float64 or cdf.dim() != 1:
+        raise ValueError("cdf must be float64[n]")
+    m = int(m)
+    if out is None:
+        out = torch.empty(max(m, 0), dtype=torch.int32, device="cuda")
+    elif out.dtype != torch.int32 or out.dim() != 1 or out.numel() < m:
+        raise ValueError(f"out must be int32 with at least {m} elements")
+    n = int(cdf.numel())
+    call("yk_sample_draw", ptr(cdf) if n else None, n, seed & (2**64 - 1), int(key) & 0xFFFFFFFF,
+         int(first) & (2**64 - 1), m, ptr(out) if m > 0 else None, stream_ptr())
+    return out[:m]
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
-           "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "_lib"]
+           "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
+           "sample_cdf", "sample_draw", "_lib"]
 
 
 def greedy_action(states):

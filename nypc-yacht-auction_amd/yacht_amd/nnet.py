@@ -301,6 +301,22 @@ class NNetWrapper:
                                dropout=a.dropout, seed=a.get("seed", 0), amp=self.uses_amp())
         return self._tr
 
+    def _sample_cdf(self, examples, states, targets, values, soft, gamma, sigma):
+        """The sampling distribution of args.trainSteps over the pooled examples: the
+        device cumulative table of recency x surprise weights.  sigma > 0 evaluates this net, as it stands,
+        on the pool once (the per-row table is freed after the weights are made)."""
+        from .replay import as_device_policies, sample_segments
+        if states.shape[0] == 0:
+            raise ValueError("trainSteps > 0 needs examples to draw from, got none")
+        lens, factors = sample_segments(examples, gamma)
+        table = None
+        if sigma > 0.0:
+            policies = soft["policies"] if soft else as_device_policies(examples)  # (none: the "visits" error)
+            table = self.yk_net().evaluate(states, targets, values, policies=tuple(policies), per_row=True)["rows"]
+        w, _ = K.sample_weights(table, lens, factors, sigma)
+        del table
+        return K.sample_cdf(w)[0]
+
     def train(self, examples, verbose=True):
         """The reference loop: `epochs` passes over shuffled minibatches of `batch_size`
         (drop_last False), one CE(argmax pi) + vloss_weight * MSE step each, clip 5.0, AdamW -
@@ -333,19 +349,34 @@ class NNetWrapper:
         of every epoch each example (board, target and, for "visits", its policy row) is replaced by a
         random member of its symmetry class, drawn on the device for (args.seed, the optimiser step count
         at that moment, the example's index) - K.augment_examples, DESIGN.md 7b-sym - into buffers
-        allocated once per call; the epoch's steps then run unchanged on that copy."""
+        allocated once per call; the epoch's steps then run unchanged on that copy.
+
+        args.trainSteps: 0 (default; the epochs of full permutations above) or T > 0 - weighted minibatch
+        sampling, a departure from the reference: the call takes exactly T steps, each
+        on batch_size examples drawn with replacement on the device (K.sample_weights / sample_cdf /
+        sample_draw) for (args.seed, the optimiser step count at the call's start, the draw's number).
+        An example's weight is sampleRecency ** age - when `examples` is a list of shards or lists, the
+        last item has age 0; any other form is one segment - times (1 - sampleSurprise) + sampleSurprise x
+        (its policy KL over the pool's mean KL), the KL of its visit policy from this net's policy as the
+        call found the net (one YkNet.evaluate over the un-augmented pool; needs the policies).  The T
+        steps are split over args.epochs rounds (round e: steps floor(e T / E) .. floor((e + 1) T / E) - 1;
+        empty rounds are skipped), a round being what an epoch is to the loss report and the symmetries."""
         from . import dist as D
-        from .replay import as_device_examples, as_device_policies
+        from .replay import as_device_examples, as_device_policies, check_sample_knobs, sample_rounds
         target = self.args.get("policy_target", "argmax")
         if target not in ("argmax", "visits"):
             raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
         symmetries = self.args.get("symmetries", ()) or ()
         symmetries = (symmetries,) if isinstance(symmetries, str) else tuple(symmetries)
         K.symmetry_flags(symmetries)  # an unknown name: ValueError, before any device work
+        T, gamma, sigma = check_sample_knobs(self.args.get("trainSteps", 0) or 0, self.args.get("sampleRecency", 1.0),
+                                             self.args.get("sampleSurprise", 0.0))
         tr = self._trainer()
         states, targets, values = as_device_examples(examples)
         # "visits": the same rows' policies as a CSR; "argmax" calls the trainer exactly as before
         soft = {"policies": as_device_policies(examples)} if target == "visits" else {}
+        cdf = self._sample_cdf(examples, states, targets, values, soft, gamma, sigma) if T else None
+        rounds, key, drawn, picks = sample_rounds(T, self.args.epochs), tr.step_count & 0xFFFFFFFF, 0, None
         pool, aug = (states, targets, soft.get("policies")), None
         if symmetries and soft:
             K.check_policy_columns(soft["policies"])
@@ -360,17 +391,26 @@ class NNetWrapper:
         g = torch.Generator(device="cuda")
         g.manual_seed(int(self.args.get("seed", 0)) + 1000003 * tr.step_count)
         for epoch in range(self.args.epochs):
+            if T and rounds[epoch][0] == rounds[epoch][1]:
+                continue  # (an empty round of the sampled steps: T < epochs)
             if symmetries and n:  # this epoch's copy of the pool (every rank holds the pool: the same copy)
                 aug = K.augment_examples(*pool, int(self.args.get("seed", 0)), tr.step_count & 0xFFFFFFFF,
                                          symmetries, out=aug)
                 states, targets = aug[0], aug[1]
                 if soft:
                     soft = {"policies": aug[2]}
-            perm = torch.randperm(n, generator=g, device="cuda").to(torch.int32)
+            if T:  # this round's steps x rows draws (every rank holds the pool: the same draws)
+                count = (rounds[epoch][1] - rounds[epoch][0]) * rows
+                if picks is None:
+                    picks = torch.empty(-(-T // self.args.epochs) * rows, dtype=torch.int32, device="cuda")
+                perm = K.sample_draw(cdf, int(self.args.get("seed", 0)), key, drawn, count, out=picks)
+                drawn += count
+            else:
+                perm, count = torch.randperm(n, generator=g, device="cuda").to(torch.int32), n
             report = verbose and (epoch % 5 == 0 or epoch == self.args.epochs - 1)
             if report:
                 tr.epoch_loss_begin(vw)  # summed on the device, read once after the epoch
-            for i in range(0, n, rows):
+            for i in range(0, count, rows):
                 idx = perm[i:i + rows]
                 if mode == "replicated":
                     tr.step(states, targets, values, idx=idx, **soft)
@@ -387,9 +427,9 @@ class NNetWrapper:
                     D.allreduce_grads(tr, weight=b / idx.numel())
                     tr.apply()
             if report:
-                total, count = tr.epoch_loss_end()
+                total, batches = tr.epoch_loss_end()
                 if rank == 0:
-                    print(f"Epoch {epoch + 1}/{self.args.epochs}, Avg Loss: {total / max(count, 1):.4f}")
+                    print(f"Epoch {epoch + 1}/{self.args.epochs}, Avg Loss: {total / max(batches, 1):.4f}")
         with torch.no_grad():
             self.nnet.load_state_dict(tr.state_dict())  # the torch copy feeds checkpoints and predict
         self._yk = None

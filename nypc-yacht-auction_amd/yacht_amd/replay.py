@@ -93,6 +93,60 @@ def check_value_knobs(value_mix, value_lambda):
     return beta, lam
 
 
+def check_sample_knobs(trainSteps=0, sampleRecency=1.0, sampleSurprise=0.0):
+    """(T, gamma, sigma) of the weighted minibatch sampling as (int, float, float):
+    trainSteps an int >= 0 (0: off - the epochs of full permutations), sampleRecency in (0, 1],
+    sampleSurprise in [0, 1].  ValueError otherwise, and when gamma != 1 or sigma != 0 while the sampling
+    is off (they would silently do nothing)."""
+    if isinstance(trainSteps, bool) or int(trainSteps) != trainSteps or trainSteps < 0:
+        raise ValueError(f"trainSteps must be an int >= 0, got {trainSteps!r}")
+    T, gamma, sigma = int(trainSteps), float(sampleRecency), float(sampleSurprise)
+    if not 0.0 < gamma <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"sampleRecency must lie in (0, 1], got {sampleRecency!r}")
+    if not 0.0 <= sigma <= 1.0:
+        raise ValueError(f"sampleSurprise must lie in [0, 1], got {sampleSurprise!r}")
+    if T == 0 and (gamma != 1.0 or sigma != 0.0):
+        raise ValueError("sampleRecency / sampleSurprise need trainSteps > 0: without it training runs "
+                         "epochs of full permutations and the weights would do nothing")
+    return T, gamma, sigma
+
+
+def sample_rounds(trainSteps: int, epochs: int):
+    """The trainSteps sampled steps split over `epochs` rounds: [(first step, one past the last)] per round,
+    round e = floor(e T / E) .. floor((e + 1) T / E) - 1; empty rounds (T < E) have first == past."""
+    T, E = int(trainSteps), int(epochs)
+    return [(e * T // E, (e + 1) * T // E) for e in range(E)]
+
+
+def _count_examples(x) -> int:
+    if isinstance(x, ExampleShard):
+        return len(x)
+    items = list(x)
+    if not items or _is_example(items[0]):
+        return len(items)
+    return sum(_count_examples(y) for y in items)
+
+
+def sample_segments(examples, gamma: float = 1.0):
+    """The sampling segments of what NNetWrapper.train takes, in as_device_examples' row order:
+    (lengths, factors).  A list of shards or lists (trainExamplesHistory) gives one segment per non-empty
+    item, item j of J weighing gamma ** (J - 1 - j) - the last iteration has age 0; anything else is one
+    segment of factor 1."""
+    if not isinstance(examples, ExampleShard):
+        items = list(examples)
+        if items and not _is_example(items[0]):
+            lens = [_count_examples(x) for x in items]
+            J = len(items)
+            segs = [(n, float(gamma) ** (J - 1 - j)) for j, n in enumerate(lens) if n]
+            if len(segs) > 64:
+                raise ValueError(f"the weighted sampling takes at most 64 non-empty history items, got {len(segs)}")
+            if segs:
+                return [n for n, _ in segs], [f for _, f in segs]
+            return [0], [1.0]
+        return [len(items)], [1.0]
+    return [len(examples)], [1.0]
+
+
 def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims: int, n_games: int = -1,
                          maxlen: int = None, stream=None, value_mix: float = 0.0,
                          value_lambda: float = 1.0) -> ExampleShard:
@@ -248,4 +302,4 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples"]
+           "augment_examples", "check_sample_knobs", "sample_rounds", "sample_segments"]
