@@ -231,6 +231,50 @@ int yk_sample_cdf(const double* w, int64_t n, double* cdf, double* total, void* 
 int yk_sample_draw(const double* cdf, int64_t n, uint64_t seed, uint32_t key, uint64_t first, int64_t m, int32_t* idx,
                    void* stream);
 
+/* ---------------------------------------------------------------- reanalysis
+ * Examples of the replay window searched again with the current net (yk_mcts_search on their boards), their
+ * policy rows replaced by the new search's visit distribution.  Not in the reference; opt-in (Coach
+ * args.reanalyseFraction / reanalyseSims, replay.reanalyse).  The only float64 operation is one division per
+ * entry, rounded on its own; everything else is integer.  No atomics on data; row offsets come from a
+ * three-pass scan (per-block sums, a scan of the sums, the add) in which no workgroup waits for another; equal
+ * inputs give equal bits.  All three synchronise `stream`.
+ *
+ * Which rows.  Row i of the call is example k = index_base + i (a global index into the window's examples,
+ * mod 2^64).  Its draw is Philox4x32-10 with counter (k lo, k hi, key, 0x10000000) - counter word 3 is 0 for the
+ * game streams, 0x20000000 for the sampling, 0x40000000 for the symmetries and 0x80000000 | move for the root
+ * noise - under key (seed lo, seed hi); x = x0 | x1 << 32, u = (x >> 11) * 2^-53 (the game streams' uniform).
+ * Row i is chosen iff u < fraction: 0 chooses none, 1 all.  DEVICE idx[0 .. m-1] = the chosen i ascending
+ * (at most `capacity` are written; idx == NULL: count only), HOST *m = their number.  YK_ERR_CAPACITY when idx is
+ * given and m > capacity.  NULL m, n < 0 or > 2^31 - 1, a fraction outside [0, 1] or NaN, capacity < 0 with
+ * idx: YK_ERR_ARG before anything touches the device.  n == 0: YK_OK, *m = 0, nothing launched. */
+int yk_reanalyse_select(int64_t n, uint64_t index_base, uint64_t seed, uint32_t key, double fraction, int32_t* idx,
+                        int64_t capacity, int64_t* m, void* stream);
+/* Visit counts as policy rows.  DEVICE counts[n][3226] (what yk_mcts_search writes).  Row r's entries are the
+ * actions a with counts[r][a] > 0, ascending (a negative count is not an entry); sum = the sequential float64
+ * sum of those counts in ascending action order (below 2^43: exact, so any order gives the same bits);
+ * pi_vals = (double)N / sum - yk_examples_policies' arithmetic for a temp-1 move; targets[r] (DEVICE, may be
+ * NULL) = the lowest action among those with the largest count (yk_examples_from_records' rule), -1 for a row
+ * without entries.  Such rows are counted in HOST *n_empty (may be NULL) and are not an error.  Two phases as
+ * yk_examples_policies: DEVICE pi_indptr[n + 1] and HOST *nnz are always written (and targets, when given);
+ * pi_cols == NULL stops there; else pi_cols[nnz], pi_vals[nnz] (YK_ERR_CAPACITY if nnz > nnz_capacity).
+ * NULL pi_indptr / nnz, NULL counts with n > 0, n < 0 or > 2^31 - 1, pi_cols without pi_vals: YK_ERR_ARG before
+ * anything touches the device. */
+int yk_policies_from_counts(const int32_t* counts, int64_t n, int64_t* pi_indptr, int32_t* pi_cols, double* pi_vals,
+                            int64_t nnz_capacity, int32_t* targets, int64_t* nnz, int64_t* n_empty, void* stream);
+/* Rows of a CSR replaced.  The old CSR (indptr[n + 1], cols, vals), DEVICE idx[m] strictly ascending within
+ * [0, n), and a new CSR of m rows (new_indptr[m + 1], new_cols, new_vals) -> the CSR (out_indptr[n + 1], out_cols,
+ * out_vals; out_indptr[0] = 0) and HOST *nnz: row idx[j] is new row j, unless that row is empty - then the old
+ * row is kept, so a failed search never deletes a target; every other row is the old row, bit for bit.
+ * out_cols == NULL: out_indptr and *nnz only; else YK_ERR_CAPACITY if nnz > nnz_capacity.  m == 0 copies the old
+ * CSR.  idx not strictly ascending or out of range is detected on the device: YK_ERR_RANGE, the outputs
+ * unspecified (nothing is written outside them).  An output that is one of the inputs, NULL indptr /
+ * out_indptr / nnz, NULL idx / new_indptr with m > 0, out_cols without out_vals or without the cols / vals it
+ * copies from, n or m < 0 or > 2^31 - 1: YK_ERR_ARG before anything touches the device. */
+int yk_policies_splice(const int64_t* indptr, const int32_t* cols, const double* vals, int64_t n, const int32_t* idx,
+                       int64_t m, const int64_t* new_indptr, const int32_t* new_cols, const double* new_vals,
+                       int64_t* out_indptr, int32_t* out_cols, double* out_vals, int64_t nnz_capacity, int64_t* nnz,
+                       void* stream);
+
 /* ---------------------------------------------------------------- self-play engine
  * Batched Coach.executeEpisode (Coach.py:34-72) over n_envs games in lock-step; every game
  * runs MCTS.getActionProb (MCTS.py:28-54) / MCTS.search (MCTS.py:56-164) with its own

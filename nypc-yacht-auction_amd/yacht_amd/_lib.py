@@ -20,7 +20,8 @@ YK_ERR_RANGE = -6
 _ERR_NAMES = {YK_ERR_ARG: "bad argument", YK_ERR_HIP: "HIP error", YK_ERR_NOMEM: "out of device memory",
               YK_ERR_CAPACITY: "engine capacity exceeded", YK_ERR_STATE: "engine state error",
               YK_ERR_RANGE: "a value outside the range the operation accepts (a net weight with |w| >= 65520, "
-                            "the fp16 split's range; sampling weights negative, NaN or without a finite positive total)"}
+                            "the fp16 split's range; sampling weights negative, NaN or without a finite positive total; "
+                            "splice rows not strictly ascending within the CSR)"}
 YK_NET_ERR_SYNC = 1  # yk_net_errors: a value-head wave timed out on the v_head.2 hand-off
 
 # per-element yk_step status -> the reference's exception (YachtGame.py:268-269, 306-307, 372, 508)
@@ -122,16 +123,20 @@ SIGNATURES = {
     "yk_sample_weights": [P, C.c_int64, P, P, I, C.c_double, C.c_int64, P, P, P],
     "yk_sample_cdf": [P, C.c_int64, P, P, P],
     "yk_sample_draw": [P, C.c_int64, U64, U32, U64, C.c_int64, P, P],
+    "yk_reanalyse_select": [C.c_int64, U64, U64, U32, C.c_double, P, C.c_int64, P, P],
+    "yk_policies_from_counts": [P, C.c_int64, P, P, P, C.c_int64, P, P, P, P],
+    "yk_policies_splice": [P, P, P, C.c_int64, P, C.c_int64, P, P, P, P, P, P, C.c_int64, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
-# search-value targets, the held-out evaluation and the weighted sampling (A/B baselines may predate them)
+# search-value targets, the held-out evaluation, the weighted sampling and the reanalysis (A/B baselines may
+# predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
-          "yk_sample_draw"}
+          "yk_sample_draw", "yk_reanalyse_select", "yk_policies_from_counts", "yk_policies_splice"}
 _lib = None
 
 

@@ -12,6 +12,9 @@ any number of ranks (one process per GPU, torch.distributed):
   an all-reduce of the gradients (DDP), so every rank holds the same new net;
 * gating: ``arena.GatingArena`` - pmcts vs nmcts as one dual-tree device batch, games sharded,
   tallies summed - then accept / reject as Coach.py:127-139.
+* reanalysis (opt-in, ``args.reanalyseFraction``; not in the reference): after the iteration's self-play, a
+  Philox-chosen fraction of every older iteration's examples is searched again with the current net and
+  their policy targets replaced (``replay.reanalyse``).  Every rank does all of it.
 * held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
   iteration that never enter training, on which the previous and the new net are evaluated after
   train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
@@ -75,6 +78,13 @@ class Coach:
         from .replay import check_sample_knobs
         check_sample_knobs(args.get("trainSteps", 0) or 0, args.get("sampleRecency", 1.0),
                            args.get("sampleSurprise", 0.0))
+        # reanalysis: reanalyseFraction of the older iterations' examples searched again with
+        # the current net every iteration, reanalyseSims simulations each (default numMCTSSims); 0 is off -
+        # no engine is built and no stream id consumed
+        from .replay import check_reanalyse_knobs
+        self.reanalyse_fraction, self.reanalyse_sims = check_reanalyse_knobs(
+            args.get("reanalyseFraction", 0.0), args.get("reanalyseSims", None), args.get("numMCTSSims", None))
+        self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
         self.holdout_eps = int(args.get("holdoutEps", 0) or 0)
         if self.holdout_eps < 0:
@@ -141,6 +151,36 @@ class Coach:
         return examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen,
                                     value_mix=self.value_mix, value_lambda=self.value_lambda)
 
+    def reanalyseWindow(self, iteration: int):
+        """The reanalysis of iteration `iteration`: every item of trainExamplesHistory but the
+        newest - whose targets the current net's search has just made - that is an ExampleShard with policies
+        has the rows yk_reanalyse_select names for (game seed, key = iteration, index_base = the item's offset
+        among the window's examples) searched again with self.nnet and is replaced in the list.  The root of
+        row j of an item's selection draws from stream _streams(m) + j.  Every rank runs all of it: the ranks
+        hold the same window and the same net and the search is exact, so they stay identical."""
+        from .replay import ExampleShard, _count_examples, reanalyse, reanalyse_select
+        prior = "hash" if getattr(self.nnet, "yk_prior", None) == "hash" else "net"
+        net = None if prior == "hash" else self.nnet.yk_net()
+        report, base, warned = [], 0, False
+        H = self.trainExamplesHistory
+        for j, item in enumerate(H[:-1]):
+            n = _count_examples(item)
+            if not isinstance(item, ExampleShard) or item.policies is None:
+                if not warned:
+                    log.warning("reanalyseFraction is set, but the window holds examples that are not device "
+                                "shards with policies (a loaded examples file): they are not reanalysed")
+                    warned = True
+            elif n:
+                idx = reanalyse_select(n, self.game.rng.seed, iteration, self.reanalyse_fraction, index_base=base)
+                m = int(idx.numel())
+                if m:
+                    H[j] = reanalyse(item, idx, net=net, prior=prior, sims=self.reanalyse_sims,
+                                     cpuct=self.args.cpuct, seed=self.game.rng.seed, env_base=self._streams(m))
+                    report.append(dict(item=j, n=n, reanalysed=m, n_empty=H[j].reanalysis["n_empty"]))
+            base += n
+        self.last_reanalysis = report
+        return report
+
     # ---- Coach.learn (Coach.py:74-139)
     def learn(self):
         """numIters iterations: numEps self-play episodes (sharded over the ranks), the replay
@@ -174,6 +214,9 @@ class Coach:
                 log.warning(f"Removing the oldest entry in trainExamples. len(trainExamplesHistory) = "
                             f"{len(self.trainExamplesHistory)}")
                 self.trainExamplesHistory.pop(0)
+            if self.reanalyse_fraction > 0.0:  # stale targets of the older iterations, before they are saved
+                self.reanalyseWindow(i)
+                t["reanalyse"] = clock()
             if rank == 0:
                 self.saveTrainExamples(i - 1)
                 self.nnet.save_checkpoint(folder=a.checkpoint, filename="temp.pth.tar")
@@ -212,7 +255,8 @@ class Coach:
             self.last_pit = (pwins, nwins, draws)
             D.barrier()
             t["gate"] = clock()
-            keys = [k for k in ("t0", "selfplay", "holdout", "save", "train", "eval", "arena", "gate") if k in t]
+            keys = [k for k in ("t0", "selfplay", "holdout", "reanalyse", "save", "train", "eval", "arena", "gate")
+                    if k in t]
             self.phase_times = {k + "_s": t[k] - t[p] for p, k in zip(keys, keys[1:])}
             if self.holdout_eps:  # eval_s: everything the held-out evaluation adds, its games included
                 self.phase_times["eval_s"] += self.phase_times.pop("holdout_s")

@@ -287,10 +287,94 @@ def sample_draw(cdf, seed: int, key: int, first: int, m: int, out=None):
     return out[:m]
 
 
+# ---------------------------------------------------------------- reanalysis
+def reanalyse_select(n: int, seed: int, key: int, fraction: float, index_base: int = 0, count_only: bool = False):
+    """Which of n examples a refresh reanalyses (yk_reanalyse_select): row i is example index_base + i of the
+    window, chosen iff its Philox uniform for (seed, key) lies below `fraction`.  Returns the chosen rows as a
+    device int32 tensor, ascending - or only their number with count_only.  Synchronises."""
+    import ctypes as C
+    n = int(n)
+    args = (n, int(index_base) & (2**64 - 1), seed & (2**64 - 1), int(key) & 0xFFFFFFFF, float(fraction))
+    m = C.c_int64()
+    call("yk_reanalyse_select", *args, None, 0, C.byref(m), stream_ptr())
+    if count_only:
+        return int(m.value)
+    idx = torch.empty(int(m.value), dtype=torch.int32, device="cuda")
+    if m.value:
+        call("yk_reanalyse_select", *args, ptr(idx), int(m.value), C.byref(m), stream_ptr())
+    return idx
+
+
+def _csr(policies):
+    if isinstance(policies, dict):
+        policies = (policies["pi_indptr"], policies["pi_cols"], policies["pi_vals"])
+    indptr, cols, vals = policies
+    if indptr.dtype != torch.int64 or cols.dtype != torch.int32 or vals.dtype != torch.float64:
+        raise TypeError("policies: pi_indptr int64, pi_cols int32, pi_vals float64")
+    if indptr.dim() != 1 or indptr.numel() < 1:
+        raise ValueError("pi_indptr needs n + 1 entries")
+    return indptr, cols, vals
+
+
+def policies_from_counts(counts):
+    """Root visit counts as policy rows (yk_policies_from_counts).  counts: device int32[n, 3226], what
+    yk_mcts_search writes.  Returns ((pi_indptr, pi_cols, pi_vals), targets int32[n], n_empty): row r holds the
+    actions with a positive count, ascending, with N / sum N in float64; targets[r] is the most visited action
+    (the lowest on ties), -1 for the n_empty rows without a positive count.  Synchronises."""
+    import ctypes as C
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != ACTION_SIZE:
+        raise ValueError(f"counts must be int32[n, {ACTION_SIZE}]")
+    n = int(counts.shape[0])
+    indptr = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    targets = torch.empty(n, dtype=torch.int32, device="cuda")
+    nnz, empty = C.c_int64(), C.c_int64()
+    cp, tp = (ptr(counts), ptr(targets)) if n else (None, None)
+    call("yk_policies_from_counts", cp, n, ptr(indptr), None, None, 0, tp, C.byref(nnz), C.byref(empty), stream_ptr())
+    k = int(nnz.value)
+    cols = torch.empty(k, dtype=torch.int32, device="cuda")
+    vals = torch.empty(k, dtype=torch.float64, device="cuda")
+    if k:
+        call("yk_policies_from_counts", cp, n, ptr(indptr), ptr(cols), ptr(vals), k, tp, C.byref(nnz), C.byref(empty),
+             stream_ptr())
+    return (indptr, cols, vals), targets, int(empty.value)
+
+
+def policies_splice(policies, idx, new_policies):
+    """Rows idx of a policy CSR replaced by the rows of another (yk_policies_splice): idx a device int32
+    tensor, strictly ascending within the old CSR's rows; new row j becomes row idx[j] unless it is empty,
+    then the old row stays.  Returns the new device CSR (pi_indptr, pi_cols, pi_vals); the inputs are not
+    modified.  ValueError for an idx that is not strictly ascending or out of range.  Synchronises."""
+    import ctypes as C
+    indptr, cols, vals = _csr(policies)
+    nip, ncols, nvals = _csr(new_policies)
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise TypeError("idx must be an int32 vector")
+    n, m = int(indptr.numel()) - 1, int(idx.numel())
+    if nip.numel() != m + 1:
+        raise ValueError(f"the new CSR has {nip.numel() - 1} rows for {m} indices")
+    out_ip = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    nnz = C.c_int64()
+    # (an empty CSR's cols / vals may have no storage: any non-null pointer does, nothing reads it)
+    src = (ptr(indptr), ptr(cols) or ptr(indptr), ptr(vals) or ptr(indptr), n, ptr(idx) if m else None, m,
+           ptr(nip) if m else None, ptr(ncols) or ptr(nip), ptr(nvals) or ptr(nip))
+    try:
+        call("yk_policies_splice", *src, ptr(out_ip), None, None, 0, C.byref(nnz), stream_ptr())
+        k = int(nnz.value)
+        out_cols = torch.empty(k, dtype=torch.int32, device="cuda")
+        out_vals = torch.empty(k, dtype=torch.float64, device="cuda")
+        if k:
+            call("yk_policies_splice", *src, ptr(out_ip), ptr(out_cols), ptr(out_vals), k, C.byref(nnz), stream_ptr())
+    except _lib.YkError as e:
+        if e.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError(f"idx must be strictly ascending within 0 .. {n - 1}") from None
+    return out_ip, out_cols, out_vals
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
-           "sample_cdf", "sample_draw", "_lib"]
+           "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice", "_lib"]
 
 
 def greedy_action(states):

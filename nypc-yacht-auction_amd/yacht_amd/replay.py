@@ -20,6 +20,7 @@ import torch
 
 from ._lib import YK_ERR_STATE, YK_OK, YkError, call, lib, stream_ptr
 from .kernels import augment_examples  # (a random symmetry of every example; listed with the buffer's functions)
+from .kernels import policies_from_counts, policies_splice, reanalyse_select  # (the reanalysis' device calls)
 
 
 def _vcap(max_moves: int, sims: int) -> int:
@@ -44,6 +45,7 @@ class ExampleShard:
         self.policies = policies
         self.outcomes = values if outcomes is None else outcomes
         self.root_values = root_values
+        self.reanalysis = None  # replay.reanalyse's report on the shard it returns: {"n", "n_empty", "chunks"}
         self._host = None
 
     def __len__(self):
@@ -202,6 +204,128 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
     return ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n], root_values=rootv[:n])
 
 
+# ---------------------------------------------------------------- reanalysis
+def check_reanalyse_knobs(reanalyseFraction=0.0, reanalyseSims=None, numMCTSSims=None):
+    """(fraction, sims) of the reanalysis as (float, int): reanalyseFraction in [0, 1] (0: off),
+    reanalyseSims an int >= 2 (default numMCTSSims; checked only when the reanalysis is on - the first
+    simulation on a fresh tree only expands the root, so one simulation leaves every count zero).
+    ValueError otherwise."""
+    f = float(0.0 if reanalyseFraction is None else reanalyseFraction)
+    if not 0.0 <= f <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"reanalyseFraction must lie in [0, 1], got {reanalyseFraction!r}")
+    sims = numMCTSSims if reanalyseSims is None else reanalyseSims
+    if reanalyseSims is not None or f > 0.0:
+        if sims is None or isinstance(sims, bool) or int(sims) != sims or int(sims) < 2:
+            raise ValueError(f"reanalyseSims must be an int >= 2, got {sims!r}")
+    return f, (int(sims) if sims is not None else 0)
+
+
+def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: int, cpuct: float, seed: int,
+              env_base: int = 0, chunk: int = 4096, env_ids=None, ctr=None) -> ExampleShard:
+    """Examples idx of a shard searched again (MuZero's reanalyse): their boards are the roots
+    of `sims` simulations of yk_mcts_search on fresh trees with `net` (a YkNet, or a wrapper with yk_net();
+    prior="hash": the test prior), and their policy rows and targets become the new search's.
+
+    idx: a device int32 tensor, strictly ascending within the shard.  The roots are searched E = min(len(idx),
+    chunk) at a time on one SelfPlayEngine(E, sims, cpuct, max_moves=1), the trees reset before every chunk.
+    Root j draws from the game stream (seed, env_base + j) from counter 0 - or from env_ids[j] / ctr[j] where
+    given.  The last, partial chunk is padded with copies of its first root on the stream ids after the
+    call's last one; their searches are dropped (they consume nothing: a stream is a function of its id).
+    No root noise is ever added.
+
+    A reanalysed row holds the visit distribution N / sum N of its new search and its target the most visited
+    action (the lowest on ties) - also where the stored row was the one-hot of a temp-0 move, so afterwards
+    the examples file no longer holds the reference's tuple for those rows.  A row whose search left no visit
+    keeps its old policy and target; `reanalysis["n_empty"]` of the returned shard counts them.
+
+    Returns a new ExampleShard (shards are immutable; host() caches): `policies` the spliced CSR with the
+    same values64, `targets` a copy with the reanalysed rows replaced; states, values, outcomes and
+    root_values are the input's tensors - the value targets keep the original search's numbers.  Its
+    `reanalysis` is {"n": len(idx), "n_empty": ..., "chunks": ...}.  ValueError for a shard without policies,
+    sims < 2 or a bad idx; an engine error raises YkError."""
+    from . import kernels as K
+    from .engine import SelfPlayEngine
+    if shard.policies is None:
+        raise ValueError("reanalyse needs the shard's policies (policies=None): build it with examples_from_images")
+    if isinstance(sims, bool) or int(sims) != sims or int(sims) < 2:
+        raise ValueError(f"sims must be an int >= 2 (one simulation on a fresh tree only expands the root), got {sims!r}")
+    if int(chunk) < 1:
+        raise ValueError(f"chunk must be >= 1, got {chunk!r}")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_cuda:
+        raise TypeError("idx must be a device int32 vector")
+    n, m = len(shard), int(idx.numel())
+    P = shard.policies
+
+    def result(pol, targets, n_empty, chunks):
+        out = ExampleShard(shard.states, targets, shard.values, policies=pol, outcomes=shard.outcomes,
+                           root_values=shard.root_values)
+        out.reanalysis = dict(n=m, n_empty=n_empty, chunks=chunks)
+        return out
+    if m == 0:
+        return result(dict(P), shard.targets.clone(), 0, 0)
+    # (checked before the gather below indexes with it; yk_policies_splice checks the same on the device)
+    if int(idx.min()) < 0 or int(idx.max()) >= n or (m > 1 and not bool((idx[1:] > idx[:-1]).all())):
+        raise ValueError(f"idx must be strictly ascending within 0 .. {n - 1}")
+    if hasattr(net, "yk_net") and prior == "net":
+        prior = "hash" if getattr(net, "yk_prior", None) == "hash" else "net"
+        net = None if prior == "hash" else net.yk_net()
+    rows = idx.to(torch.int64)
+    roots = shard.states.index_select(0, rows).contiguous()
+    E = min(m, int(chunk))
+    pad = (-m) % E
+    if env_ids is None:
+        env = np.arange(m + pad, dtype=np.uint64) + np.uint64(int(env_base) & 0xFFFFFFFF)
+    else:
+        env = np.asarray(torch.as_tensor(env_ids).cpu().numpy(), dtype=np.int64).astype(np.uint64).reshape(-1)
+        if env.size != m:
+            raise ValueError(f"env_ids has {env.size} entries for {m} roots")
+        env = np.concatenate([env, (env[-1] & np.uint64(0xFFFFFFFF)) + np.uint64(1) + np.arange(pad, dtype=np.uint64)])
+    env = torch.from_numpy((env & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)).to("cuda")
+    c0 = torch.zeros(m + pad, dtype=torch.int64, device="cuda")
+    if ctr is not None:
+        c_in = torch.as_tensor(ctr).to(device="cuda", dtype=torch.int64).reshape(-1)
+        if c_in.numel() != m:
+            raise ValueError(f"ctr has {c_in.numel()} entries for {m} roots")
+        c0[:m] = c_in
+    sp = stream_ptr()
+    counts = torch.empty((E, K.ACTION_SIZE), dtype=torch.int32, device="cuda")
+    eng = SelfPlayEngine(E, int(sims), float(cpuct), net=net, prior=prior, max_moves=1)
+    parts, tparts, n_empty, chunks = [], [], 0, 0
+    try:
+        for j0 in range(0, m, E):
+            k = min(E, m - j0)
+            r = roots[j0:j0 + k]
+            if k < E:  # the padding: copies of the chunk's first root
+                r = torch.cat([r, r[:1].expand(E - k, 8)]).contiguous()
+            # the roots of a chunk are unrelated to the last chunk's, and a tree refuses a root of a lower round
+            call("yk_mcts_reset", eng.handle)
+            try:
+                call("yk_mcts_search", eng.handle, r.data_ptr(), seed & (2**64 - 1), env[j0:j0 + E].data_ptr(),
+                     c0[j0:j0 + E].data_ptr(), int(sims), counts.data_ptr(), sp)
+            except YkError as e:
+                st = eng.stats()
+                bits = [b_name for b, b_name in eng.ERROR_BITS.items() if st["errors"] & b]
+                raise YkError(f"yk_mcts_search [reanalysis chunk at root {j0}: {', '.join(bits)}; stats {st}]",
+                              e.code) from None
+            pol, tg, ne = K.policies_from_counts(counts[:k])
+            parts.append(pol)
+            tparts.append(tg)
+            n_empty += ne
+            chunks += 1
+    finally:
+        eng.close()
+    new = _cat_csr(parts, torch) if len(parts) > 1 else parts[0]
+    if new is None:  # (no chunk has rows: cannot happen with m > 0)
+        new = parts[0]
+    out_ip, out_cols, out_vals = K.policies_splice((P["pi_indptr"], P["pi_cols"], P["pi_vals"]), idx, new)
+    t_new = torch.cat(tparts) if len(tparts) > 1 else tparts[0]
+    targets = shard.targets.clone()
+    keep = t_new >= 0
+    targets[rows[keep]] = t_new[keep]
+    pol = dict(P, pi_indptr=out_ip, pi_cols=out_cols, pi_vals=out_vals)
+    return result(pol, targets, n_empty, chunks)
+
+
 # ---------------------------------------------------------------- what NNetWrapper.train takes
 def _is_example(x) -> bool:
     return isinstance(x, tuple) and len(x) == 3 and not isinstance(x[0], (ExampleShard, list, deque))
@@ -302,4 +426,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_sample_knobs", "sample_rounds", "sample_segments"]
+           "augment_examples", "check_sample_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]
