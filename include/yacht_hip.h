@@ -21,6 +21,8 @@
  *    (seed, env_id, counter) of Philox4x32-10 draws; each die, tie-break, tie pick and
  *    sampling uniform consumes one counter value.  Given the same draws the results
  *    are identical to the reference (tests/test_oracle_golden.py, tests/test_gpu_*.py).
+ *    Counter word 3 is the domain of a draw (0 for the game streams); the domains the
+ *    entry points below name are listed once, in csrc/yk_philox.h.
  *  - No torch types cross this boundary.
  */
 #ifndef YACHT_HIP_H

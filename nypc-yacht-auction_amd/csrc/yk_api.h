@@ -31,22 +31,48 @@ inline RecordLayout record_layout(int64_t E, int64_t M, int64_t VCAP) {
     L.total = off;
     return L;
 }
+
+// YK_ERR_HIP (and the error kept for yk_last_hip_error) unless `e` is hipSuccess
+inline int hip_rc(hipError_t e) {
+    if (e == hipSuccess) return YK_OK;
+    set_hip_error(e);
+    return YK_ERR_HIP;
+}
+// after a kernel launch: whether the launch was accepted
+inline int launched() { return hip_rc(hipGetLastError()); }
+// drops the error a failed hipMalloc leaves behind (its caller reports YK_ERR_NOMEM)
+inline void clear_hip_error() { (void)hipGetLastError(); }
+
+// One stream-ordered device allocation (alloc() once).  Its hipFreeAsync is issued by release(), or by the
+// destructor on every path that returns before it: an early return cannot leak.  Where the free has to
+// precede a hipStreamSynchronize, call release() before it.
+struct Scratch {
+    void* p = nullptr;
+    hipStream_t st;
+    explicit Scratch(hipStream_t s) : st(s) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { (void)release(); }
+    int alloc(size_t bytes) {
+        const int rc = hip_rc(hipMallocAsync(&p, bytes, st));
+        if (rc != YK_OK) p = nullptr;
+        return rc;
+    }
+    hipError_t release() {  // (not recorded: after an earlier error the caller ignores it, and that error stays)
+        void* q = p;
+        p = nullptr;
+        return q ? hipFreeAsync(q, st) : hipSuccess;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
 }  // namespace yk
 
-#define YK_HIP(call)                                   \
+// return the YK_* code of `call` unless it is YK_OK
+#define YK_TRY(call)                                   \
     do {                                               \
-        hipError_t e_ = (call);                        \
-        if (e_ != hipSuccess) {                        \
-            yk::set_hip_error(e_);                     \
-            return YK_ERR_HIP;                         \
-        }                                              \
+        const int rc_ = (call);                        \
+        if (rc_ != YK_OK) return rc_;                  \
     } while (0)
-
-#define YK_LAUNCHED()                                  \
-    do {                                               \
-        hipError_t e_ = hipGetLastError();             \
-        if (e_ != hipSuccess) {                        \
-            yk::set_hip_error(e_);                     \
-            return YK_ERR_HIP;                         \
-        }                                              \
-    } while (0)
+#define YK_HIP(call) YK_TRY(yk::hip_rc(call))
+#define YK_LAUNCHED() YK_TRY(yk::launched())

@@ -21,7 +21,6 @@ namespace {
 
 constexpr int AUG_CARRY = 1, AUG_ROLLS = 2, AUG_GROUPS = 4;
 constexpr int DRAW_P1 = 0, DRAW_P2 = 16, DRAW_A = 32, DRAW_B = 40, DRAW_SWAP = 48;  // first draw of each list
-constexpr uint32_t AUG_DOMAIN = 0x40000000u;  // counter word 3 (game streams: 0; root noise: 0x80000000 | move)
 constexpr uint64_t IDENT = 0x9876543210ull;   // the identity permutation of 10 positions as nibbles
 constexpr int64_t AUG_MAX_GRID = 1 << 30;
 
@@ -66,37 +65,13 @@ constexpr bool rank_is_combo_order() {
 static_assert(rank_is_combo_order(), "rank table == index in COMB_5_OF_10 order");
 __constant__ RankTab c_rank = make_rank();
 
-// word 1 of Philox4x32-10 with counter (i, k, t, AUG_DOMAIN) under key (seed lo, seed hi)
-__device__ __forceinline__ uint32_t aug_x1(uint32_t i, uint32_t k, uint32_t t, uint64_t seed) {
-    uint32_t c0 = i, c1 = k, c2 = t, c3 = AUG_DOMAIN;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c1;
-}
-__device__ __forceinline__ uint32_t wave_draw(uint32_t x1, int i) {  // lane i's draw (i wave-uniform, 0..63)
-    return (uint32_t)__builtin_amdgcn_readlane((int)x1, i);
-}
-__device__ __forceinline__ uint64_t wave_word(uint64_t v, int i) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), i) << 32);
-}
-
-// Fisher-Yates over L <= 10 positions with first draw b: perm = [0 .. L-1]; for m = L-1 .. 1:
-// j = below_{b + (L-1-m)}(m + 1), swap perm[m], perm[j].  Nibble i of the result is perm[i]; i >= L: i.
+// Fisher-Yates over L <= 10 positions with first draw b (lane i of x1 holds draw i): perm = [0 .. L-1];
+// for m = L-1 .. 1: j = below_{b + (L-1-m)}(m + 1), swap perm[m], perm[j].  Nibble i of the result is
+// perm[i]; i >= L: i.
 __device__ __forceinline__ uint64_t fisher_yates(int L, int b, uint32_t x1) {
     uint64_t perm = IDENT;
     for (int m = L - 1; m >= 1; m--) {
-        const int j = (int)(((uint64_t)wave_draw(x1, b + (L - 1 - m)) * (uint32_t)(m + 1)) >> 32);
+        const int j = (int)(((uint64_t)lane_val(x1, b + (L - 1 - m)) * (uint32_t)(m + 1)) >> 32);
         const uint64_t pm = (perm >> (4 * m)) & 0xF, pj = (perm >> (4 * j)) & 0xF;
         perm = (perm & ~(0xFull << (4 * m)) & ~(0xFull << (4 * j))) | (pj << (4 * m)) | (pm << (4 * j));
     }
@@ -164,10 +139,12 @@ __global__ __launch_bounds__(64) void k_augment(const yk_state_t* states, const 
     const int lane = threadIdx.x;
     const int64_t r = row0 + (int64_t)blockIdx.x;
     const uint64_t mine = lane < 8 ? states[r].w[lane] : 0;
-    const uint32_t x1 = aug_x1((uint32_t)lane, (uint32_t)(uint64_t)(index_base + r), epoch_key, seed);
+    // draw `lane` of this example: word 1 of the Philox output
+    const uint32_t x1 =
+        philox4x32_10(seed, (uint32_t)lane, (uint32_t)(uint64_t)(index_base + r), epoch_key, PHILOX_SYMMETRY).x1;
     YkS s;
 #pragma unroll
-    for (int i = 0; i < 8; i++) s.w[i] = wave_word(mine, i);
+    for (int i = 0; i < 8; i++) s.w[i] = lane_val(mine, i);
 
     // ---- the state (wave-uniform)
     const int n1 = min(wa_n(s.w[1]), 10), n2 = min(wa_n(s.w[4]), 10);
@@ -184,7 +161,7 @@ __global__ __launch_bounds__(64) void k_augment(const yk_state_t* states, const 
         if (hasA) rA = permute_nibbles(rA, fisher_yates(5, DRAW_A, x1), 5);
         if (hasB) rB = permute_nibbles(rB, fisher_yates(5, DRAW_B, x1), 5);
     }
-    const bool swap = (flags & AUG_GROUPS) && (wave_draw(x1, DRAW_SWAP) >> 31);
+    const bool swap = (flags & AUG_GROUPS) && (lane_val(x1, DRAW_SWAP) >> 31);
     if (swap) {
         uint64_t t = rA;
         rA = rB;
@@ -228,7 +205,7 @@ __global__ __launch_bounds__(64) void k_augment(const yk_state_t* states, const 
     __syncthreads();
     const uint32_t p0 = (uint32_t)__popc(s_bits[lane]), p1 = lane + 64 < MASK_WORDS ? (uint32_t)__popc(s_bits[lane + 64]) : 0u;
     const uint32_t i0 = wave_inclusive_scan(p0, lane), i1 = wave_inclusive_scan(p1, lane);
-    const uint32_t first64 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 63);
+    const uint32_t first64 = lane_val(i0, 63);
     s_below[lane] = i0 - p0;
     if (lane + 64 < MASK_WORDS) s_below[lane + 64] = first64 + i1 - p1;
     __syncthreads();

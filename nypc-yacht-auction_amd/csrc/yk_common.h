@@ -17,6 +17,7 @@
 #include <climits>
 
 #include "yacht_hip.h"
+#include "yk_philox.h"
 
 namespace yk {
 
@@ -114,21 +115,9 @@ __device__ __host__ inline bool all_used(const YkS& s, int p) {  // both_scored_
 }
 
 // ------------------------------------------------------------------ RNG contract (oracle/spec.py)
+// draw `ctr` of game `env`'s stream (yk_philox.h)
 __device__ __host__ inline uint64_t philox_draw(uint64_t seed, uint32_t env, uint64_t ctr) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = env, c3 = 0;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (uint64_t)c0 | ((uint64_t)c1 << 32);
+    return philox_u64(philox4x32_10(seed, (uint32_t)ctr, (uint32_t)(ctr >> 32), env, PHILOX_GAME));
 }
 // Dropout keep masks of the trainers (yk_train.hip, yk_train_amp.hip): element e (= global row x H
 // + column) of layer `layer` at optimiser step `step` is kept iff its 16-bit uniform - bits
@@ -167,7 +156,7 @@ struct Stream {
     __device__ __host__ uint64_t next() { return philox_draw(seed, env, ctr++); }
     __device__ __host__ int below(int n) { return (int)(((next() >> 32) * (uint64_t)n) >> 32); }
     __device__ __host__ int die() { return 1 + below(6); }
-    __device__ __host__ double uniform53() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
+    __device__ __host__ double uniform53() { return u53(next()); }
     // roll_five  YachtGame.py:154-155 -> 5 nibbles
     __device__ __host__ uint64_t roll5() {
         uint64_t r = 0;
@@ -546,8 +535,15 @@ __device__ __forceinline__ T xlane_sum(T v) {
     return v + xlane<1>(v);
 }
 // lane f's value (f wave-uniform): v_readlane instead of a ds_bpermute
+__device__ __forceinline__ uint32_t lane_val(uint32_t v, int f) { return (uint32_t)__builtin_amdgcn_readlane((int)v, f); }
 __device__ __forceinline__ float lane_val(float v, int f) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), f));
+    return __builtin_bit_cast(float, lane_val(__builtin_bit_cast(uint32_t, v), f));
+}
+__device__ __forceinline__ uint64_t lane_val(uint64_t v, int f) {
+    return (uint64_t)lane_val((uint32_t)v, f) | ((uint64_t)lane_val((uint32_t)(v >> 32), f) << 32);
+}
+__device__ __forceinline__ double lane_val(double v, int f) {
+    return __builtin_bit_cast(double, lane_val(__builtin_bit_cast(uint64_t, v), f));
 }
 // argmax butterfly over the wave: the largest value, the lowest index among equals, on every lane
 // (the same pairs as a __shfl_xor butterfly, so the same result)

@@ -1373,7 +1373,7 @@ template <class T>
 int dalloc(yk_engine* eng, T** p, size_t count) {
     void* q = nullptr;
     if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        (void)hipGetLastError();
+        clear_hip_error();
         return YK_ERR_NOMEM;
     }
     eng->allocs.push_back(q);

@@ -238,19 +238,15 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
     if (n == 0) return YK_OK;
     hipStream_t s = as_stream(stream);
     const size_t nwork = (size_t)(NPART + 1) * NCOL, nrows = rows ? 0 : (size_t)n * NCOL;
-    double* work = nullptr;
-    YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&work), sizeof(double) * (nwork + nrows), s));
+    Scratch buf(s);
+    YK_TRY(buf.alloc(sizeof(double) * (nwork + nrows)));
+    double* work = buf.as<double>();
     double* out = rows ? rows : work + nwork;
     launch_rows(logits, ld, v, states, targets, values, Csr{pi_indptr, pi_cols, pi_vals}, batch_idx, 0, (int)n, out,
                 s);
-    hipError_t e = hipGetLastError();
-    int rc = YK_OK;
-    if (e != hipSuccess) {
-        set_hip_error(e);
-        rc = YK_ERR_HIP;
-    }
+    int rc = launched();
     if (rc == YK_OK) rc = reduce_to_host(out, n, work, sums, s);
-    (void)hipFreeAsync(work, s);
+    (void)buf.release();
     YK_HIP(hipStreamSynchronize(s));
     return rc;
 }
@@ -268,8 +264,9 @@ int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targ
     // one allocation: logits[ch][PI_LD] f32 | v[ch] f32 (padded to 8 B) | work | rows (when not given)
     const size_t nf = (size_t)ch * PI_LD + (((size_t)ch + 1) & ~(size_t)1);
     const size_t nwork = (size_t)(NPART + 1) * NCOL, nrows = rows ? 0 : (size_t)n * NCOL;
-    float* logits = nullptr;
-    YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&logits), sizeof(float) * nf + sizeof(double) * (nwork + nrows), s));
+    Scratch buf(s);
+    YK_TRY(buf.alloc(sizeof(float) * nf + sizeof(double) * (nwork + nrows)));
+    float* logits = buf.as<float>();
     float* v = logits + (size_t)ch * PI_LD;
     double* work = reinterpret_cast<double*>(logits + nf);
     double* out = rows ? rows : work + nwork;
@@ -281,14 +278,10 @@ int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targ
         rc = launch_forward(net->dev, idx ? states : states + c0, nullptr, idx, nullptr, m, logits, v, s);
         if (rc != YK_OK) break;
         launch_rows(logits, PI_LD, v, states, targets, values, p, idx, c0, m, out + c0 * NCOL, s);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_hip_error(e);
-            rc = YK_ERR_HIP;
-        }
+        rc = launched();
     }
     if (rc == YK_OK) rc = reduce_to_host(out, n, work, sums, s);
-    (void)hipFreeAsync(logits, s);
+    (void)buf.release();
     YK_HIP(hipStreamSynchronize(s));
     return rc;
 }

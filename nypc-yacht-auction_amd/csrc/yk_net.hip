@@ -310,12 +310,12 @@ static int predict_common(yk_net_t* net, const yk_state_t* states, const float* 
     if (!net || !pi || !v || n < 0) return YK_ERR_ARG;
     if (n == 0) return YK_OK;
     hipStream_t s = as_stream(stream);
-    float* logits = nullptr;
-    YK_HIP(hipMallocAsync((void**)&logits, sizeof(float) * ((size_t)n * PI_LD + 2 * (size_t)n), s));
+    Scratch buf(s);  // released when the launches are queued
+    YK_TRY(buf.alloc(sizeof(float) * ((size_t)n * PI_LD + 2 * (size_t)n)));
+    float* logits = buf.as<float>();
     float2* mlse = reinterpret_cast<float2*>(logits + (size_t)n * PI_LD);
     int rc = launch_forward(net->dev, states, x, nullptr, nullptr, n, logits, v, s, nullptr, mlse);
     if (rc == YK_OK) rc = launch_softmax(logits, mlse, pi, n, s);
-    (void)hipFreeAsync(logits, s);
     return rc;
 }
 
@@ -333,19 +333,15 @@ int yk_net_leaf_prior(yk_net_t* net, const yk_state_t* states, float* pi, float*
     if (!net || !states || !pi || !v || n < 0) return YK_ERR_ARG;
     if (n == 0) return YK_OK;
     hipStream_t s = as_stream(stream);
-    float* logits = nullptr;
-    YK_HIP(hipMallocAsync((void**)&logits, sizeof(float) * ((size_t)n * PI_LD + 2 * (size_t)n), s));
+    Scratch buf(s);  // released when the launches are queued
+    YK_TRY(buf.alloc(sizeof(float) * ((size_t)n * PI_LD + 2 * (size_t)n)));
+    float* logits = buf.as<float>();
     float2* mlse = reinterpret_cast<float2*>(logits + (size_t)n * PI_LD);
     int rc = launch_forward(net->dev, states, nullptr, nullptr, nullptr, n, logits, v, s, nullptr, mlse, true);
     if (rc == YK_OK) {
         hipLaunchKernelGGL(k_leaf_prior, dim3((n + 3) / 4), dim3(256), 0, s, logits, mlse, states, pi, n);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            yk::set_hip_error(e);
-            rc = YK_ERR_HIP;
-        }
+        rc = launched();
     }
-    (void)hipFreeAsync(logits, s);
     return rc;
 }
 
@@ -354,19 +350,15 @@ int yk_net_policy_action(yk_net_t* net, const yk_state_t* states, int32_t* actio
     if (!net || !states || !actions || n < 0) return YK_ERR_ARG;
     if (n == 0) return YK_OK;
     hipStream_t s = as_stream(stream);
-    float *logits = nullptr, *v = nullptr;
-    YK_HIP(hipMallocAsync((void**)&logits, sizeof(float) * ((size_t)n * PI_LD + n), s));
-    v = logits + (size_t)n * PI_LD;
+    Scratch buf(s);  // released when the launches are queued
+    YK_TRY(buf.alloc(sizeof(float) * ((size_t)n * PI_LD + n)));
+    float* logits = buf.as<float>();
+    float* v = logits + (size_t)n * PI_LD;
     int rc = launch_forward(net->dev, states, nullptr, nullptr, nullptr, n, logits, v, s);
     if (rc == YK_OK) {
         hipLaunchKernelGGL(k_policy_pick, dim3((n + 3) / 4), dim3(256), 0, s, logits, states, actions, probs, n);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            yk::set_hip_error(e);
-            rc = YK_ERR_HIP;
-        }
+        rc = launched();
     }
-    (void)hipFreeAsync(logits, s);
     return rc;
 }
 

@@ -3,9 +3,8 @@
 // block_dirichlet, is shared by the engine's k_root_noise and by yk_dirichlet_noise, so the noise a
 // search sees and the noise the standalone entry point returns are the same bits.
 //
-// Counter domain.  A game's draw stream is Philox4x32-10 with counter (ctr lo, ctr hi, env, 0).
-// The noise uses counter (i, j, env, 0x80000000 | move): word 3 is never 0, so no noise draw can
-// coincide with a draw of any game stream, and the game's own counter is not advanced.
+// Counter domain (yk_philox.h): the noise uses counter (i, j, env, PHILOX_NOISE | move), so no noise draw
+// can coincide with a draw of any game stream, and the game's own counter is not advanced.
 //
 // All arithmetic is f64 without contraction (-ffp-contract=off): an accept test of the rejection
 // loop then differs between this code and a host restatement only when it lands within an ulp or
@@ -23,21 +22,8 @@ constexpr int NOISE_MAX_TRIES = 4096;  // rejection-loop bound (acceptance > 0.9
 
 // uniform in (0, 1) from draw i of valid action j: ((x >> 11) + 0.5) 2^-53, the sum rounded to f64
 __device__ __host__ inline double noise_u53(uint64_t seed, uint32_t env, uint32_t move, uint32_t j, uint32_t i) {
-    uint32_t c0 = i, c1 = j, c2 = env, c3 = 0x80000000u | move;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint64_t x = (uint64_t)c0 | ((uint64_t)c1 << 32);
-    return ((double)(x >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const uint64_t x = philox_u64(philox4x32_10(seed, i, j, env, PHILOX_NOISE | move));
+    return ((double)(x >> 11) + 0.5) * TWO_M53;
 }
 
 // Gamma(alpha, 1) of valid action j: Marsaglia-Tsang, alpha < 1 boosted by u^(1 / alpha)

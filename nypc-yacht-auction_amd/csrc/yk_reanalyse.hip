@@ -4,121 +4,29 @@
 // before.  -ffp-contract=off: the one float64 operation per entry (N / sum) is rounded on its own, so
 // tests/reanalyse_ref.py's numpy restatement matches bit for bit.
 //
-// No atomics on data, and nothing depends on the order in which workgroups run.  Row offsets come from a
-// three-pass exclusive scan of int64 row lengths: every block of 256 rows scans its own rows and leaves its
-// total (k_rows_scan), one workgroup scans the blocks' totals (k_blocks_scan, yk_replay.hip's k_scan_inplace
-// over them), and every block adds its offset (k_rows_add).  Integer sums: the order cannot change a bit.
+// No atomics on data, and nothing depends on the order in which workgroups run.  Row offsets come from
+// yk_scan.h's three-pass exclusive scan of int64 row lengths (scan_rows).
 #include <math.h>
-
-#include <algorithm>
 
 #include "yk_api.h"
 #include "yk_common.h"
+#include "yk_scan.h"
 
 using namespace yk;
 
 namespace {
 
 constexpr int ASIZE_ = YK_ACTION_SIZE;
-constexpr int SCAN_ROWS = 256;                     // rows per block of the scan's first and third pass
-constexpr int BSCAN_THREADS = 1024;                // the one workgroup of the second pass
-constexpr int ROWS_PER_BLOCK = 4;                  // wave-per-row kernels: 4 waves of 64 per block
-constexpr uint32_t REANALYSE_DOMAIN = 0x10000000u;  // counter word 3 (game streams 0, sampling 0x20000000,
-                                                   // symmetries 0x40000000, root noise 0x80000000 | move)
-
-// ---------------------------------------------------------------- the scan
-// Pass 1: block b's rows a[256 b ..] become their exclusive prefix within the block; bsum[b] = their total.
-__global__ __launch_bounds__(SCAN_ROWS) void k_rows_scan(int64_t* __restrict__ a, int64_t n, int64_t* __restrict__ bsum) {
-    __shared__ int64_t part[SCAN_ROWS];
-    const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * SCAN_ROWS + t;
-    const int64_t x = i < n ? a[i] : 0;
-    part[t] = x;
-    __syncthreads();
-    for (int d = 1; d < SCAN_ROWS; d <<= 1) {  // Hillis-Steele inclusive scan
-        const int64_t y = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += y;
-        __syncthreads();
-    }
-    if (i < n) a[i] = part[t] - x;
-    if (t == SCAN_ROWS - 1) bsum[blockIdx.x] = part[t];
-}
-
-// Pass 2: in-place exclusive scan of b[0..nb) into b[0..nb], b[nb] = the total.  One workgroup, a contiguous
-// chunk per thread (k_scan_inplace of yk_replay.hip).
-__global__ __launch_bounds__(BSCAN_THREADS) void k_blocks_scan(int64_t* b, int64_t nb) {
-    __shared__ int64_t part[BSCAN_THREADS];
-    const int t = threadIdx.x;
-    const int64_t chunk = (nb + BSCAN_THREADS - 1) / BSCAN_THREADS;
-    const int64_t i0 = std::min<int64_t>((int64_t)t * chunk, nb), i1 = std::min<int64_t>(i0 + chunk, nb);
-    int64_t s = 0;
-    for (int64_t i = i0; i < i1; i++) s += b[i];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < BSCAN_THREADS; d <<= 1) {
-        const int64_t x = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    int64_t run = part[t] - s;
-    for (int64_t i = i0; i < i1; i++) {
-        const int64_t x = b[i];
-        b[i] = run;
-        run += x;
-    }
-    if (t == BSCAN_THREADS - 1) b[nb] = part[t];
-}
-
-// Pass 3: a[i] += the offset of i's block; a[n] = the total.
-__global__ __launch_bounds__(SCAN_ROWS) void k_rows_add(int64_t* __restrict__ a, int64_t n, const int64_t* __restrict__ bsum,
-                                                        int64_t nb) {
-    const int64_t i = (int64_t)blockIdx.x * SCAN_ROWS + threadIdx.x;
-    if (i < n) a[i] += bsum[blockIdx.x];
-    if (i == n) a[n] = bsum[nb];  // (the grid covers n + 1 elements)
-}
-
-// a[0..n) row lengths -> a[0..n] exclusive offsets, a[n] the total; bsum: DEVICE int64[blocks_of(n) + 1]
-inline int64_t blocks_of(int64_t n) { return (n + SCAN_ROWS - 1) / SCAN_ROWS; }
-int scan_rows(int64_t* a, int64_t n, int64_t* bsum, hipStream_t st) {
-    const int64_t nb = blocks_of(n);
-    if (nb > 0) {
-        hipLaunchKernelGGL(k_rows_scan, dim3((unsigned)nb), dim3(SCAN_ROWS), 0, st, a, n, bsum);
-        YK_LAUNCHED();
-    }
-    hipLaunchKernelGGL(k_blocks_scan, dim3(1), dim3(BSCAN_THREADS), 0, st, bsum, nb);
-    YK_LAUNCHED();
-    hipLaunchKernelGGL(k_rows_add, dim3((unsigned)blocks_of(n + 1)), dim3(SCAN_ROWS), 0, st, a, n, bsum, nb);
-    YK_LAUNCHED();
-    return YK_OK;
-}
+constexpr int ROWS_PER_BLOCK = 4;  // wave-per-row kernels: 4 waves of 64 per block
 
 // ---------------------------------------------------------------- select
-__device__ __forceinline__ uint64_t philox_select(uint64_t seed, uint32_t key, uint64_t k) {
-    uint32_t c0 = (uint32_t)k, c1 = (uint32_t)(k >> 32), c2 = key, c3 = REANALYSE_DOMAIN;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (uint64_t)c0 | ((uint64_t)c1 << 32);
-}
-
 // pos[i] = 1 when row i is chosen (u < fraction), else 0
 __global__ __launch_bounds__(256) void k_select_flags(int64_t n, uint64_t index_base, uint64_t seed, uint32_t key,
                                                       double fraction, int64_t* __restrict__ pos) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint64_t x = philox_select(seed, key, index_base + (uint64_t)i);
-    const double u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
+    const uint64_t k = index_base + (uint64_t)i;
+    const double u = u53(philox_u64(philox4x32_10(seed, (uint32_t)k, (uint32_t)(k >> 32), key, PHILOX_REANALYSE)));
     pos[i] = u < fraction ? 1 : 0;
 }
 
@@ -166,15 +74,15 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void k_counts_rows(const int32
 }
 
 // *out = #{r : len[r] == 0}.  One workgroup; an integer sum.
-__global__ __launch_bounds__(BSCAN_THREADS) void k_count_empty(const int64_t* __restrict__ len, int64_t n,
+__global__ __launch_bounds__(SCAN_THREADS) void k_count_empty(const int64_t* __restrict__ len, int64_t n,
                                                                int64_t* __restrict__ out) {
-    __shared__ int64_t part[BSCAN_THREADS];
+    __shared__ int64_t part[SCAN_THREADS];
     const int t = threadIdx.x;
     int64_t s = 0;
-    for (int64_t i = t; i < n; i += BSCAN_THREADS) s += len[i] == 0;
+    for (int64_t i = t; i < n; i += SCAN_THREADS) s += len[i] == 0;
     part[t] = s;
     __syncthreads();
-    for (int d = BSCAN_THREADS / 2; d > 0; d >>= 1) {
+    for (int d = SCAN_THREADS / 2; d > 0; d >>= 1) {
         if (t < d) part[t] += part[t + d];
         __syncthreads();
     }
@@ -276,15 +184,6 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void k_splice_fill(
     }
 }
 
-struct Scratch {  // one stream-ordered allocation, released on every path
-    void* p = nullptr;
-    hipStream_t st;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    ~Scratch() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -298,14 +197,13 @@ int yk_reanalyse_select(int64_t n, uint64_t index_base, uint64_t seed, uint32_t 
     hipStream_t st = as_stream(stream);
     const int64_t nb = blocks_of(n);
     Scratch s(st);  // pos[n + 1] | bsum[nb + 1]
-    YK_HIP(hipMallocAsync(&s.p, sizeof(int64_t) * (size_t)(n + 1 + nb + 1), st));
-    int64_t* pos = static_cast<int64_t*>(s.p);
+    YK_TRY(s.alloc(sizeof(int64_t) * (size_t)(n + 1 + nb + 1)));
+    int64_t* pos = s.as<int64_t>();
     int64_t* bsum = pos + n + 1;
     hipLaunchKernelGGL(k_select_flags, dim3((unsigned)grid_for(n, 256)), dim3(256), 0, st, n, index_base, seed, key,
                        fraction, pos);
     YK_LAUNCHED();
-    int rc = scan_rows(pos, n, bsum, st);
-    if (rc != YK_OK) return rc;
+    YK_TRY(scan_rows(pos, n, bsum, st));
     if (idx && capacity > 0) {
         hipLaunchKernelGGL(k_select_write, dim3((unsigned)grid_for(n, 256)), dim3(256), 0, st, pos, n, capacity, idx);
         YK_LAUNCHED();
@@ -324,18 +222,17 @@ int yk_policies_from_counts(const int32_t* counts, int64_t n, int64_t* pi_indptr
     hipStream_t st = as_stream(stream);
     const int64_t nb = blocks_of(n);
     Scratch s(st);  // bsum[nb + 1] | the empty rows' count
-    YK_HIP(hipMallocAsync(&s.p, sizeof(int64_t) * (size_t)(nb + 2), st));
-    int64_t* bsum = static_cast<int64_t*>(s.p);
+    YK_TRY(s.alloc(sizeof(int64_t) * (size_t)(nb + 2)));
+    int64_t* bsum = s.as<int64_t>();
     int64_t* dempty = bsum + nb + 1;
     if (n > 0) {
         hipLaunchKernelGGL(k_counts_rows, dim3((unsigned)grid_for(n, ROWS_PER_BLOCK)), dim3(64 * ROWS_PER_BLOCK), 0, st,
                            counts, n, pi_indptr, targets);
         YK_LAUNCHED();
     }
-    hipLaunchKernelGGL(k_count_empty, dim3(1), dim3(BSCAN_THREADS), 0, st, pi_indptr, n, dempty);
+    hipLaunchKernelGGL(k_count_empty, dim3(1), dim3(SCAN_THREADS), 0, st, pi_indptr, n, dempty);
     YK_LAUNCHED();
-    int rc = scan_rows(pi_indptr, n, bsum, st);
-    if (rc != YK_OK) return rc;
+    YK_TRY(scan_rows(pi_indptr, n, bsum, st));
     int64_t total = 0, empty = 0;
     YK_HIP(hipMemcpyAsync(&total, pi_indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     YK_HIP(hipMemcpyAsync(&empty, dempty, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -367,8 +264,8 @@ int yk_policies_splice(const int64_t* indptr, const int32_t* cols, const double*
     hipStream_t st = as_stream(stream);
     const int64_t nb = blocks_of(n);
     Scratch s(st);  // bsum[nb + 1] | src[n] | the flag word
-    YK_HIP(hipMallocAsync(&s.p, sizeof(int64_t) * (size_t)(nb + 1) + sizeof(int32_t) * (size_t)(n + 1), st));
-    int64_t* bsum = static_cast<int64_t*>(s.p);
+    YK_TRY(s.alloc(sizeof(int64_t) * (size_t)(nb + 1) + sizeof(int32_t) * (size_t)(n + 1)));
+    int64_t* bsum = s.as<int64_t>();
     int32_t* src = reinterpret_cast<int32_t*>(bsum + nb + 1);
     int* flag = reinterpret_cast<int*>(src + n);
     YK_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
@@ -387,8 +284,7 @@ int yk_policies_splice(const int64_t* indptr, const int32_t* cols, const double*
                            out_indptr);
         YK_LAUNCHED();
     }
-    int rc = scan_rows(out_indptr, n, bsum, st);
-    if (rc != YK_OK) return rc;
+    YK_TRY(scan_rows(out_indptr, n, bsum, st));
     int64_t total = 0;
     int bad = 0;
     YK_HIP(hipMemcpyAsync(&total, out_indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));

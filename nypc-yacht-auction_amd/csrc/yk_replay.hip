@@ -74,32 +74,6 @@ __global__ void __launch_bounds__(64) k_pi_counts(ImgView v, const int64_t* off,
     }
 }
 
-// In-place exclusive scan of a[0..n) into a[0..n], a[n] = the total.  One workgroup, a contiguous
-// chunk per thread (as k_example_offsets).
-__global__ void __launch_bounds__(SCAN_THREADS) k_scan_inplace(int64_t* a, int64_t n) {
-    __shared__ int64_t part[SCAN_THREADS];
-    const int t = threadIdx.x;
-    const int64_t chunk = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int64_t i0 = min<int64_t>((int64_t)t * chunk, n), i1 = min<int64_t>(i0 + chunk, n);
-    int64_t s = 0;
-    for (int64_t i = i0; i < i1; i++) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-        const int64_t x = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    int64_t run = part[t] - s;
-    for (int64_t i = i0; i < i1; i++) {
-        const int64_t x = a[i];
-        a[i] = run;
-        run += x;
-    }
-    if (t == SCAN_THREADS - 1) a[n] = part[t];
-}
-
 // Pass 2: the entries (cols ascending, vals = N / sum N in float64, MCTS.py:52-54) and the float64
 // values of the kept examples.
 __global__ void __launch_bounds__(64) k_pi_fill(ImgView v, const int64_t* off, int64_t skip, int64_t cap,
@@ -145,15 +119,14 @@ int yk_examples_from_records(const void* images, int n_images, int n_envs, int m
         return YK_ERR_ARG;
     if (states && (!targets || !values || capacity < 0)) return YK_ERR_ARG;
     hipStream_t s = as_stream(stream);
-    Prep p;
-    const int rc = prepare(images, n_images, n_envs, max_moves, sims, n_games, s, &p);
-    if (rc != YK_OK) return rc;
+    Prep p(s);
+    YK_TRY(prepare(images, n_images, n_envs, max_moves, sims, n_games, &p));
     if (states && p.n_games > 0 && capacity > 0) {
-        hipLaunchKernelGGL(k_examples, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.off, skip, capacity, states,
-                           targets, values);
+        hipLaunchKernelGGL(k_examples, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.offsets(), skip, capacity,
+                           states, targets, values);
         YK_LAUNCHED();
     }
-    YK_HIP(hipFreeAsync(p.off, s));
+    YK_HIP(p.off.release());
     YK_HIP(hipStreamSynchronize(s));
     int64_t n = p.total - skip;
     n = n < 0 ? 0 : n;
@@ -169,16 +142,12 @@ int yk_examples_policies(const void* images, int n_images, int n_envs, int max_m
         !pi_indptr || !nnz || (pi_cols && !pi_vals))
         return YK_ERR_ARG;
     hipStream_t s = as_stream(stream);
-    Prep p;
-    const int rc = prepare(images, n_images, n_envs, max_moves, sims, n_games, s, &p);
-    if (rc != YK_OK) return rc;
+    Prep p(s);
+    YK_TRY(prepare(images, n_images, n_envs, max_moves, sims, n_games, &p));
     YK_HIP(hipStreamSynchronize(s));
-    if (n_examples > p.total - skip) {  // asks for examples the images do not hold
-        YK_HIP(hipFree(p.off));
-        return YK_ERR_ARG;
-    }
+    if (n_examples > p.total - skip) return YK_ERR_ARG;  // asks for examples the images do not hold
     if (p.n_games > 0 && n_examples > 0) {
-        hipLaunchKernelGGL(k_pi_counts, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.off, skip, n_examples,
+        hipLaunchKernelGGL(k_pi_counts, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.offsets(), skip, n_examples,
                            pi_indptr);
         YK_LAUNCHED();
     }
@@ -191,11 +160,11 @@ int yk_examples_policies(const void* images, int n_images, int n_envs, int max_m
     if (pi_cols && total > nnz_capacity) {
         err = YK_ERR_CAPACITY;
     } else if (pi_cols && p.n_games > 0 && n_examples > 0) {
-        hipLaunchKernelGGL(k_pi_fill, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.off, skip, n_examples,
+        hipLaunchKernelGGL(k_pi_fill, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.offsets(), skip, n_examples,
                            pi_indptr, pi_cols, pi_vals, values);
         YK_LAUNCHED();
     }
-    YK_HIP(hipFreeAsync(p.off, s));
+    YK_HIP(p.off.release());
     YK_HIP(hipStreamSynchronize(s));
     *nnz = total;
     return err;

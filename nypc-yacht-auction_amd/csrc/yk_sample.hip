@@ -27,8 +27,6 @@ constexpr int DRAWS = 4;                           // k_draw: draws a thread loc
 constexpr int DRAW_BLOCKS = 256;                   // k_draw: blocks before a thread takes more than one draw (the CUs)
 constexpr int DRAW_MAX_BLOCKS = 1024;              // k_draw: the largest grid; past it a thread takes further groups
 constexpr int KSUM_FLIGHT = 32;                    // k_sample_ksum: loads in flight per thread
-constexpr uint32_t SAMPLE_DOMAIN = 0x20000000u;    // counter word 3 (game streams 0, symmetries 0x40000000,
-                                                   // root noise 0x80000000 | move)
 constexpr int COL_S = 5, COL_CE = 6, COL_H = 7;    // yk_net_evaluate's columns: mass, soft CE, target entropy
 
 // ---------------------------------------------------------------- weights
@@ -174,23 +172,6 @@ __global__ __launch_bounds__(256) void k_sample_add(double* __restrict__ cdf, in
 static_assert(CHUNK == 256, "k_sample_add: one block per chunk");
 
 // ---------------------------------------------------------------- draw
-__device__ __forceinline__ uint64_t philox_sample(uint64_t seed, uint32_t key, uint64_t j) {
-    uint32_t c0 = (uint32_t)j, c1 = (uint32_t)(j >> 32), c2 = key, c3 = SAMPLE_DOMAIN;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (uint64_t)c0 | ((uint64_t)c1 << 32);
-}
-
 // DRAWS searches advanced in lock step, so that their loads overlap (one search is a chain of
 // floor(log2 nchunks) + 9 dependent loads, 20 at 3840 chunks): out[d] = #{i < n : cdf[i] <= t[d]} (UPPER) or #{i < n : cdf[i] < t[d]}, the flat bound over the
 // nondecreasing cdf[0..n) in two levels - the chunk by the chunks' ends (every 256th element of cdf itself:
@@ -256,8 +237,8 @@ __global__ __launch_bounds__(256) void k_sample_draw(const double* __restrict__ 
         bool past = false;
 #pragma unroll
         for (int d = 0; d < DRAWS; d++) {
-            const uint64_t x = philox_sample(seed, key, first + (uint64_t)(r0 + d * stride));
-            const double u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
+            const uint64_t j = first + (uint64_t)(r0 + d * stride);
+            const double u = u53(philox_u64(philox4x32_10(seed, (uint32_t)j, (uint32_t)(j >> 32), key, PHILOX_SAMPLE)));
             // (a draw past m searches for -1: every lane's probes then fall on the same elements; not stored)
             t[d] = r0 + d * stride < m ? u * total : -1.0;
         }
@@ -280,11 +261,6 @@ __global__ __launch_bounds__(256) void k_sample_draw(const double* __restrict__ 
     }
 }
 
-int check_launch() {
-    YK_LAUNCHED();
-    return YK_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -298,16 +274,16 @@ int yk_sample_weights(const double* rows, int64_t ld, const int64_t* seg_ptr, co
     for (int s = 0; s < nseg; s++)
         if (seg_ptr[s + 1] < seg_ptr[s] || !(seg_factor[s] >= 0.0) || !std::isfinite(seg_factor[s])) return YK_ERR_ARG;
     hipStream_t st = as_stream(stream);
-    double* K = nullptr;
+    Scratch K(st);
     *ksum = 0.0;
     int rc = YK_OK;
     if (rows) {
-        YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&K), sizeof(double), st));
+        YK_TRY(K.alloc(sizeof(double)));
         hipLaunchKernelGGL(k_sample_kl, dim3((unsigned)grid_for(n, 256)), dim3(256), 0, st, rows, ld, n, w);
-        rc = check_launch();
+        rc = launched();
         if (rc == YK_OK) {
-            hipLaunchKernelGGL(k_sample_ksum, dim3(1), dim3(NPART), 0, st, w, n, K);
-            rc = check_launch();
+            hipLaunchKernelGGL(k_sample_ksum, dim3(1), dim3(NPART), 0, st, w, n, K.as<double>());
+            rc = launched();
         }
     }
     const double* kin = rows && surprise != 0.0 ? w : nullptr;
@@ -315,13 +291,12 @@ int yk_sample_weights(const double* rows, int64_t ld, const int64_t* seg_ptr, co
         const int64_t a = seg_ptr[s], len = seg_ptr[s + 1] - a;
         if (len == 0) continue;
         hipLaunchKernelGGL(k_sample_weights, dim3((unsigned)grid_for(len, 256)), dim3(256), 0, st,
-                           kin ? kin + a : nullptr, K, len, (double)n, surprise, seg_factor[s], w + a);
-        rc = check_launch();
+                           kin ? kin + a : nullptr, K.as<double>(), len, (double)n, surprise, seg_factor[s], w + a);
+        rc = launched();
     }
-    if (K) {
-        if (rc == YK_OK && hipMemcpyAsync(ksum, K, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) rc = YK_ERR_HIP;
-        (void)hipFreeAsync(K, st);
-    }
+    if (K.p && rc == YK_OK && hipMemcpyAsync(ksum, K.p, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = YK_ERR_HIP;
+    (void)K.release();
     YK_HIP(hipStreamSynchronize(st));
     return rc;
 }
@@ -331,28 +306,29 @@ int yk_sample_cdf(const double* w, int64_t n, double* cdf, double* total, void* 
     hipStream_t st = as_stream(stream);
     const int64_t nchunks = (n + CHUNK - 1) / CHUNK;
     // one allocation: O[nchunks + 1] | the flag word
-    double* O = nullptr;
-    YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&O), sizeof(double) * (size_t)(nchunks + 2), st));
+    Scratch buf(st);
+    YK_TRY(buf.alloc(sizeof(double) * (size_t)(nchunks + 2)));
+    double* O = buf.as<double>();
     int* flag = reinterpret_cast<int*>(O + nchunks + 1);
     int rc = YK_OK, bad = 0;
     double tot = 0.0;
     if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) rc = YK_ERR_HIP;
     if (rc == YK_OK) {
         hipLaunchKernelGGL(k_sample_scan, dim3((unsigned)grid_for(nchunks, SCAN_CPB)), dim3(256), 0, st, w, n, cdf, flag);
-        rc = check_launch();
+        rc = launched();
     }
     if (rc == YK_OK) {
         hipLaunchKernelGGL(k_sample_offsets, dim3(1), dim3(256), 0, st, cdf, n, nchunks, O);
-        rc = check_launch();
+        rc = launched();
     }
     if (rc == YK_OK) {
         hipLaunchKernelGGL(k_sample_add, dim3((unsigned)nchunks), dim3(256), 0, st, cdf, n, O);
-        rc = check_launch();
+        rc = launched();
     }
     if (rc == YK_OK && (hipMemcpyAsync(&tot, cdf + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
                         hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = YK_ERR_HIP;
-    (void)hipFreeAsync(O, st);
+    (void)buf.release();
     YK_HIP(hipStreamSynchronize(st));
     if (rc != YK_OK) return rc;
     *total = tot;

@@ -574,7 +574,7 @@ template <class T>
 int talloc(yk_trainer* t, T** p, size_t count) {
     void* q = nullptr;
     if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        (void)hipGetLastError();
+        clear_hip_error();
         return YK_ERR_NOMEM;
     }
     t->allocs.push_back(q);
@@ -722,7 +722,7 @@ int gemm_rm(hipStream_t s, float* ws, bool ta, bool tb, int M, int N, int K, con
     if (S > 1)
         hipLaunchKernelGGL(k_sgemm_reduce, dim3((unsigned)(((long)M * N + 255) / 256)), dim3(256), 0, s, M, N, S, ws, C,
                            ldc, beta);
-    return hipGetLastError() == hipSuccess ? YK_OK : YK_ERR_HIP;
+    return launched();
 }
 
 template <int VPL>

@@ -1794,7 +1794,7 @@ template <class T>
 int aalloc(AmpTrain* a, T** p, size_t count) {
     void* q = nullptr;
     if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        (void)hipGetLastError();
+        clear_hip_error();
         return YK_ERR_NOMEM;
     }
     a->allocs.push_back(q);

@@ -11,13 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ double lane_f64(double x, int src) {  // x of lane `src` (wave-uniform), to every lane
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), src);
-    return __longlong_as_double((long long)((uint64_t)lo | ((uint64_t)hi << 32)));
-}
-
 // One wavefront per game.  The game's moves are taken 64 at a time from the last chunk down, lane i move
 // c0 + i; within a chunk the backward recursion runs from the chunk's last move to its first, every lane
 // carrying the same (G_{t+1}, W_{t+1}) in uniform registers and lane i keeping G of its own move - no LDS.
@@ -54,8 +47,8 @@ __global__ void __launch_bounds__(64) k_value_targets(ImgView v, const int64_t* 
             const uint64_t has = __ballot(in && word != 0u);
             for (int i = min(63, n - 1 - c0); i >= 0; i--) {
                 const int t = c0 + i;
-                const double Wt = lane_f64(W, i);
-                const double Gt = t == n - 1 ? lane_f64(Z, i) : keep_l * Wn + lambda * G;
+                const double Wt = lane_val(W, i);
+                const double Gt = t == n - 1 ? lane_val(Z, i) : keep_l * Wn + lambda * G;
                 if (lane == i) {
                     Gm = Gt;
                     need_later = absent_later;
@@ -90,26 +83,22 @@ extern "C" int yk_examples_value_targets(const void* images, int n_images, int n
         (!values && n_examples > 0))
         return YK_ERR_ARG;
     hipStream_t s = as_stream(stream);
-    Prep p;
-    const int rc = prepare(images, n_images, n_envs, max_moves, sims, n_games, s, &p);
-    if (rc != YK_OK) return rc;
+    Prep p(s);
+    YK_TRY(prepare(images, n_images, n_envs, max_moves, sims, n_games, &p));
     YK_HIP(hipStreamSynchronize(s));
-    if (n_examples > p.total - skip) {  // asks for examples the images do not hold
-        YK_HIP(hipFree(p.off));
-        return YK_ERR_ARG;
-    }
-    unsigned long long* miss = nullptr;
+    if (n_examples > p.total - skip) return YK_ERR_ARG;  // asks for examples the images do not hold
+    Scratch miss(s);
     unsigned long long host_miss = 0;
     if (p.n_games > 0 && n_examples > 0) {
-        YK_HIP(hipMallocAsync(reinterpret_cast<void**>(&miss), sizeof(*miss), s));
-        YK_HIP(hipMemsetAsync(miss, 0, sizeof(*miss), s));
-        hipLaunchKernelGGL(k_value_targets, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.off, skip, n_examples,
-                           beta, lambda, values, root_values, miss);
+        YK_TRY(miss.alloc(sizeof(host_miss)));
+        YK_HIP(hipMemsetAsync(miss.p, 0, sizeof(host_miss), s));
+        hipLaunchKernelGGL(k_value_targets, dim3((unsigned)p.n_games), dim3(64), 0, s, p.v, p.offsets(), skip,
+                           n_examples, beta, lambda, values, root_values, miss.as<unsigned long long>());
         YK_LAUNCHED();
-        YK_HIP(hipMemcpyAsync(&host_miss, miss, sizeof(host_miss), hipMemcpyDeviceToHost, s));
-        YK_HIP(hipFreeAsync(miss, s));
+        YK_HIP(hipMemcpyAsync(&host_miss, miss.p, sizeof(host_miss), hipMemcpyDeviceToHost, s));
+        YK_HIP(miss.release());
     }
-    YK_HIP(hipFreeAsync(p.off, s));
+    YK_HIP(p.off.release());
     YK_HIP(hipStreamSynchronize(s));
     if (n_missing) *n_missing = (int64_t)host_miss;
     return host_miss ? YK_ERR_STATE : YK_OK;

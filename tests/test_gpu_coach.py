@@ -98,6 +98,16 @@ def test_examples_kernel_matches_host_restatements(Y):
     _same_csr(shard.host(), h)
     _same_csr(tail.host(), h, skip=len(ref) - 1000)
     _same_csr(part.host(), h)
+    # (the whole batch's CSR is 4608 rows: every thread of the one-workgroup scan owns 5 of them.)  The image
+    # 11 times over is 1056 games - the example offsets' scan then owns two games per thread - and gives the
+    # single image's examples 11 times over
+    many = R.examples_from_images(torch.stack([img] * 11), n, 48, sims).host()
+    one = shard.host()
+    for k in ("states", "targets", "values", "pi_cols", "pi_vals"):
+        assert np.array_equal(many[k], np.concatenate([one[k]] * 11)), k
+    nnz = int(one["pi_indptr"][-1])
+    assert np.array_equal(many["pi_indptr"],
+                          np.concatenate([[0]] + [one["pi_indptr"][1:] + r * nnz for r in range(11)]))
     # lazy reference tuples of a shard
     b, pi, v = tail[0]
     assert pi == ref[len(ref) - 1000][1] and v == ref[len(ref) - 1000][2]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import reanalyse_ref as RR
+import sample_ref as SR
 from oracle import spec
 
 pytestmark = pytest.mark.gpu
@@ -53,14 +54,19 @@ def _rows(csr):
 _U = {}
 
 
+N_BIG = 256 * 1024 + 1  # 1025 blocks of 256 rows: thread 0 of the scan's middle pass owns two block sums
+
+
 def _uniforms(base):
     if base not in _U:
-        _U[base] = np.asarray([RR.uniform(SEED, 5, base + i) for i in range(4096)])
+        # the numpy Philox of tests/sample_ref.py in this domain, held to the restatement over the first 4096
+        _U[base] = SR.uniforms(SEED, 5, base, N_BIG, domain=RR.DOMAIN)
+        assert np.array_equal(_U[base][:4096], np.asarray([RR.uniform(SEED, 5, base + i) for i in range(4096)]))
     return _U[base]
 
 
 @pytest.mark.parametrize("base", [0, 2**32 - 3])  # (the second crosses counter word 0 into word 1)
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 4096])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 4096, N_BIG])
 def test_select_is_the_restatement(Y, n, base):
     from yacht_amd._lib import YK_ERR_CAPACITY
     lib, K = Y[0].lib(), Y[2]
