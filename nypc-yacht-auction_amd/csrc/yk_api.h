@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
+#include <vector>
+
 #include "yacht_hip.h"
 
 namespace yk {
@@ -66,6 +69,35 @@ struct Scratch {
     template <class T>
     T* as() const { return static_cast<T*>(p); }
 };
+
+// The persistent hipMalloc blocks of one handle (engine, trainer, net): the destructor frees them all,
+// so a handle that owns one cannot leak its device memory on any path that destroys it.
+struct DeviceBlocks {
+    std::vector<void*> blocks;
+    DeviceBlocks() = default;
+    DeviceBlocks(const DeviceBlocks&) = delete;
+    DeviceBlocks& operator=(const DeviceBlocks&) = delete;
+    ~DeviceBlocks() {
+        for (void* p : blocks) (void)hipFree(p);
+    }
+    // `count` elements (0: one, so the pointer is always valid); YK_ERR_NOMEM, the HIP error dropped, else
+    template <class T>
+    int alloc(T** p, size_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
+            clear_hip_error();
+            return YK_ERR_NOMEM;
+        }
+        blocks.push_back(q);
+        *p = static_cast<T*>(q);
+        return YK_OK;
+    }
+};
+// The state_dict tensors that are weight matrices (packed to fp16 by yk_net_create, cast to fp16 by the
+// mixed-precision trainer): input_fc.weight 0, block b's fc1.weight 4 + 8 b and fc2.weight 8 + 8 b,
+// pi_head.2.weight 6 + 8 NB, v_head.2.weight 10 + 8 NB.  Whether fp16(w) is finite for every finite weight
+// of them: |w| >= 65520 rounds to inf, where torch's float32 holds a number.  (yk_net.hip)
+bool matrices_fit_fp16(const float* const* params, int H, int NB);
 }  // namespace yk
 
 // return the YK_* code of `call` unless it is YK_OK

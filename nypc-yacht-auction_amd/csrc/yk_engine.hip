@@ -1285,7 +1285,7 @@ struct yk_engine {
     hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;
     int fparts_single = 1, fparts_dual = 0;  // fparts_dual 0: the two forwards stay in sequence
     EngDev d{};
-    std::vector<void*> allocs;
+    DeviceBlocks mem;  // every device array below and in d / nz
     float* logits = nullptr;
     float* vpred = nullptr;
     float2* mlse = nullptr;
@@ -1318,6 +1318,23 @@ struct yk_engine {
     bool noise = false;
     bool have_priors = false;    // the last batch was a self-play batch with noise: yk_engine_root_priors
     bool root_values = false;    // record_root_values: k_root_value after each k_move_end of yk_selfplay
+    yk_engine() = default;
+    yk_engine(const yk_engine&) = delete;
+    yk_engine& operator=(const yk_engine&) = delete;
+    ~yk_engine() {  // (also of a half-made engine: yk_engine_create's early returns)
+        for (auto& L : pg)
+            for (hipEvent_t e : L.ev) (void)hipEventDestroy(e);
+        for (int g = 0; g < YK_MAX_GROUPS; g++) {
+            if (gs[g]) (void)hipStreamDestroy(gs[g]);
+            if (ev_join[g]) (void)hipEventDestroy(ev_join[g]);
+            if (ev_fwd[g]) (void)hipEventDestroy(ev_fwd[g]);
+        }
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (dstream) (void)hipStreamDestroy(dstream);
+        if (ev_d0) (void)hipEventDestroy(ev_d0);
+        if (ev_d1) (void)hipEventDestroy(ev_d1);
+        if (host_done) (void)hipHostFree(host_done);
+    }
 };
 
 namespace {
@@ -1369,17 +1386,6 @@ dim3 game_grid(const EngDev& d) {
     return dim3((unsigned)std::max(1, (d.e_hi - d.e_lo + GAMES_PER_BLOCK - 1) / GAMES_PER_BLOCK));
 }
 
-template <class T>
-int dalloc(yk_engine* eng, T** p, size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        clear_hip_error();
-        return YK_ERR_NOMEM;
-    }
-    eng->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return YK_OK;
-}
 int check_errors(yk_engine* eng, hipStream_t s) {
     uint32_t err = 0;
     uint32_t nerr[2] = {0u, 0u};
@@ -1495,7 +1501,7 @@ int yk_engine_create(yk_engine_t** out, const yk_engine_config_t* cfg, yk_net_t*
     if (cfg->prior != 0 && cfg->prior != 1) return YK_ERR_ARG;
     // root noise: alpha >= 0, eps in [0, 1] (NaN fails both); on when both are > 0
     if (!(cfg->dirichlet_alpha >= 0.0) || !(cfg->dirichlet_eps >= 0.0 && cfg->dirichlet_eps <= 1.0)) return YK_ERR_ARG;
-    yk_engine* eng = new yk_engine();
+    std::unique_ptr<yk_engine> eng(new yk_engine());  // (owned here until *out is set: every return before frees it)
     eng->cfg = *cfg;
     eng->net = net;
     EngDev& d = eng->d;
@@ -1558,9 +1564,7 @@ constexpr int YK_FPARTS_MAX = 4;
     }
     const size_t R = ((size_t)cfg->n_envs + d.rec_stride - 1) / d.rec_stride;
     const size_t E = (size_t)d.E, T = (size_t)d.T;
-    int rc = YK_OK;
-#define A(p, n) \
-    if (rc == YK_OK) rc = dalloc(eng, &(p), (n))
+#define A(p, n) YK_TRY(eng->mem.alloc(&(p), (n)))
     for (int g = 0; g < 2; g++) {
         A(d.nodes[g], T * d.NCAP);
         A(d.hidx[g], T * d.HCAP);
@@ -1631,7 +1635,7 @@ constexpr int YK_FPARTS_MAX = 4;
         A(d.rec_leaf, R * (size_t)d.max_exp);
     }
 #undef A
-    if (rc == YK_OK && hipHostMalloc((void**)&eng->host_done, sizeof(int32_t)) != hipSuccess) rc = YK_ERR_NOMEM;
+    if (hipHostMalloc((void**)&eng->host_done, sizeof(int32_t)) != hipSuccess) return YK_ERR_NOMEM;
     {  // YK_ROOT_SCAN=0: every descent scans the root's whole compact set (A/B, and the test that both
        // give the same trees)
         const char* ev = getenv("YK_ROOT_SCAN");
@@ -1648,23 +1652,20 @@ constexpr int YK_FPARTS_MAX = 4;
         const char* es = getenv("YK_SPLIT_DESCENT");
         eng->split_descent = es && es[0] == '1';
     }
-    if (rc == YK_OK && G > 1) {
-        if (hipEventCreateWithFlags(&eng->ev_fork, hipEventDisableTiming) != hipSuccess) rc = YK_ERR_HIP;
-        for (int g = 0; g < G && rc == YK_OK; g++)
+    // (these report YK_ERR_HIP without recording the HIP error)
+    if (G > 1) {
+        if (hipEventCreateWithFlags(&eng->ev_fork, hipEventDisableTiming) != hipSuccess) return YK_ERR_HIP;
+        for (int g = 0; g < G; g++)
             if (hipStreamCreateWithFlags(&eng->gs[g], hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&eng->ev_join[g], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&eng->ev_fwd[g], hipEventDisableTiming) != hipSuccess)
-                rc = YK_ERR_HIP;
+                return YK_ERR_HIP;
     }
-    if (rc == YK_OK && eng->fparts_dual > 0) {
+    if (eng->fparts_dual > 0) {
         if (hipStreamCreateWithFlags(&eng->dstream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&eng->ev_d0, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&eng->ev_d1, hipEventDisableTiming) != hipSuccess)
-            rc = YK_ERR_HIP;
-    }
-    if (rc != YK_OK) {
-        yk_engine_destroy(eng);
-        return rc;
+            return YK_ERR_HIP;
     }
     d.logits = eng->logits;
     d.vpred = eng->vpred;
@@ -1681,25 +1682,11 @@ constexpr int YK_FPARTS_MAX = 4;
     for (size_t i = 0; i < E; i++) ids[i] = (uint32_t)i;
     YK_HIP(hipMemcpy(eng->mcts_env, ids.data(), sizeof(uint32_t) * E, hipMemcpyHostToDevice));
     YK_HIP(hipDeviceSynchronize());
-    *out = eng;
+    *out = eng.release();
     return YK_OK;
 }
 
 int yk_engine_destroy(yk_engine_t* eng) {
-    if (!eng) return YK_OK;
-    for (auto& L : eng->pg)
-        for (hipEvent_t e : L.ev) (void)hipEventDestroy(e);
-    for (int g = 0; g < YK_MAX_GROUPS; g++) {
-        if (eng->gs[g]) (void)hipStreamDestroy(eng->gs[g]);
-        if (eng->ev_join[g]) (void)hipEventDestroy(eng->ev_join[g]);
-        if (eng->ev_fwd[g]) (void)hipEventDestroy(eng->ev_fwd[g]);
-    }
-    if (eng->ev_fork) (void)hipEventDestroy(eng->ev_fork);
-    if (eng->dstream) (void)hipStreamDestroy(eng->dstream);
-    if (eng->ev_d0) (void)hipEventDestroy(eng->ev_d0);
-    if (eng->ev_d1) (void)hipEventDestroy(eng->ev_d1);
-    for (void* p : eng->allocs) (void)hipFree(p);
-    if (eng->host_done) (void)hipHostFree(eng->host_done);
     delete eng;
     return YK_OK;
 }

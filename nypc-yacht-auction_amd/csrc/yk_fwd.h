@@ -237,12 +237,6 @@ __device__ __forceinline__ void layernorm(float (&x)[VPL], const float* g, const
 // operation, as numpy does); the forward's LayerNorm row passes - VALU-bound and on every layer's
 // critical path - contract their multiply-adds into v_pk_fma_f32 (one rounding instead of two: no
 // less accurate than torch's own LayerNorm kernels, which fuse them too).  Scoped per function.
-#ifndef FWD_SYNC_MODE
-// (A/B) how a timed-out value-head wait is reported: 0 not at all, 1 LDS flag from a re-read of the
-// count + the net's error word at the end, 2 NaN v for the tile, 3 LDS flag from the loop count + error word,
-// 4 the error word written right after the wait (loop count)
-#define FWD_SYNC_MODE 1
-#endif
 #define YK_ROW_CONTRACT _Pragma("clang fp contract(fast)")
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
@@ -1136,16 +1130,8 @@ __device__ __forceinline__ void forward_tile(NetDev net, const yk_state_t* __res
         // (reads of X stay after the count's: compiler fence; a timeout is flagged, reported at the
         // kernel's very end, where a global write adds no wait to any load in flight)
         __atomic_signal_fence(__ATOMIC_ACQUIRE);
-        const bool lost = it >= (1 << 20);  // (wave-uniform)
-        (void)lost;
-#if FWD_SYNC_MODE == 1
+        // (timed out if the count, read again, is still short)
         if (lane == 0 && __hip_atomic_load(&VHC, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < NVW) SYNC_LOST = 1u;
-#elif FWD_SYNC_MODE == 3
-        if (lost && lane == 0) SYNC_LOST = 1u;
-#elif FWD_SYNC_MODE == 4
-        // (here, in the older waves' slack before the end: only their own logit stores are in flight)
-        if (lost && lane == 0 && net.err) atomicOr(net.err, FWD_ERR_SYNC);
-#endif
 #pragma unroll
         for (int rr = 0; rr < ROWS / 4; rr++) {
             const int r = wave * (ROWS / 4) + rr;
@@ -1153,11 +1139,7 @@ __device__ __forceinline__ void forward_tile(NetDev net, const yk_state_t* __res
             const float* wv2 = VS + VS_BV1 * H + 128;
             float s = silu(X[r * LD + 2 * lane]) * wv2[2 * lane] + silu(X[r * LD + 2 * lane + 1]) * wv2[2 * lane + 1];
             s = wave_sum(s);
-#if FWD_SYNC_MODE == 2
-            const float vv = lost ? __builtin_nanf("") : tanhf(s + bv2);  // (a timed-out hand-off: NaN, never stale)
-#else
             const float vv = tanhf(s + bv2);
-#endif
             if (lane == 0 && part == 0 && row < n && ((amask >> r) & 1u)) vout[row] = vv;  // active rows only
         }
     }
@@ -1210,9 +1192,7 @@ __device__ __forceinline__ void forward_tile(NetDev net, const yk_state_t* __res
     }
     // the last statement: a branch around a global atomic earlier would merge the wait counters of
     // its paths at the join and drain the policy ring's loads in flight (section 8-)
-#if FWD_SYNC_MODE == 1 || FWD_SYNC_MODE == 3
     if (wave < 4 && lane == 0 && SYNC_LOST && net.err) atomicOr(net.err, FWD_ERR_SYNC);
-#endif
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "yacht_hip.h"
+#include "yk_api.h"
 
 namespace yk {
 
@@ -56,6 +57,5 @@ int launch_softmax(const float* logits, const float2* mlse, float* pi, int n, hi
 
 struct yk_net {
     yk::NetDev dev;
-    float* blob;  // single device allocation holding every tensor
-    size_t bytes;
+    yk::DeviceBlocks mem;  // one block holding every tensor
 };

@@ -156,6 +156,17 @@ int launch_softmax(const float* logits, const float2* mlse, float* pi, int n, hi
     return YK_OK;
 }
 
+bool matrices_fit_fp16(const float* const* p, int H, int NB) {
+    auto fits = [](const float* w, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (std::isfinite(w[i]) && std::fabs(w[i]) >= 65520.f) return false;
+        return true;
+    };
+    for (int b = 0; b < NB; b++)
+        if (!fits(p[4 + 8 * b], (size_t)H * H) || !fits(p[8 + 8 * b], (size_t)H * H)) return false;
+    return fits(p[0], (size_t)H * FEAT) && fits(p[6 + 8 * NB], (size_t)ASIZE * H) && fits(p[10 + 8 * NB], (size_t)128 * H);
+}
+
 }  // namespace yk
 
 extern "C" {
@@ -197,20 +208,7 @@ int yk_net_create(yk_net_t** out, int H, int NB, const float* const* p, int npar
     const size_t o_err = put(1);  // the forwards' check flags (a uint32 word, zeroed below)
     // the f32-equivalent split's range: hi = fp16(w) must be finite for every finite weight of the
     // packed (MFMA) matrices - |w| >= 65520 rounds to inf, where torch's float32 holds a number
-    {
-        const int mats[4] = {0, 6 + 8 * NB, 10 + 8 * NB, -1};
-        const size_t mlen[3] = {(size_t)H * FEAT, (size_t)ASIZE * H, (size_t)128 * H};
-        auto out_of_range = [](const float* w, size_t n) {
-            for (size_t i = 0; i < n; i++)
-                if (std::isfinite(w[i]) && std::fabs(w[i]) >= 65520.f) return true;
-            return false;
-        };
-        for (int m = 0; mats[m] >= 0; m++)
-            if (out_of_range(p[mats[m]], mlen[m])) return YK_ERR_RANGE;
-        for (int b = 0; b < NB; b++)
-            if (out_of_range(p[4 + 8 * b], (size_t)H * H) || out_of_range(p[8 + 8 * b], (size_t)H * H))
-                return YK_ERR_RANGE;
-    }
+    if (!matrices_fit_fp16(p, H, NB)) return YK_ERR_RANGE;
     // pi_head.2 bounds for the valid-only softmax (k_forward): bias spread, largest weight-row norm
     float pi_bmin = INFINITY, pi_bmax = -INFINITY, pi_wmax = 0.f;
     {
@@ -253,18 +251,11 @@ int yk_net_create(yk_net_t** out, int H, int NB, const float* const* p, int npar
         dup(d0 + 3 * H, o_b2 + v0, H); dup(d0 + 4 * H, o_g2 + v0, H); dup(d0 + 5 * H, o_be2 + v0, H);
     }
 
-    yk_net* net = new yk_net();
-    net->bytes = h.size() * sizeof(float);
-    if (hipMalloc(&net->blob, net->bytes) != hipSuccess) {
-        delete net;
-        return YK_ERR_NOMEM;
-    }
-    if (hipMemcpy(net->blob, h.data(), net->bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(net->blob);
-        delete net;
-        return YK_ERR_HIP;
-    }
-    const float* B = net->blob;
+    std::unique_ptr<yk_net> net(new yk_net());  // (until *out is set: every return before frees it)
+    float* blob = nullptr;                      // the single device allocation holding every tensor
+    YK_TRY(net->mem.alloc(&blob, h.size()));
+    if (hipMemcpy(blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return YK_ERR_HIP;
+    const float* B = blob;
     NetDev& d = net->dev;
     d.H = H; d.NB = NB;
     d.planes = 2;  // f32-equivalent (yk_net_set_precision switches to the fp16 mode)
@@ -274,12 +265,12 @@ int yk_net_create(yk_net_t** out, int H, int NB, const float* const* p, int npar
     d.g_pi = B + o_gpi; d.be_pi = B + o_bepi; d.w_pi = B + o_wpi; d.b_pi = B + o_bpi;
     d.g_v = B + o_gv; d.be_v = B + o_bev; d.w_v1 = B + o_wv1; d.b_v1 = B + o_bv1; d.w_v2 = B + o_wv2; d.b_v2 = B + o_bv2;
     d.vstat = B + o_vs; d.vblk = B + o_vb;
-    d.err = reinterpret_cast<uint32_t*>(net->blob + o_err);
+    d.err = reinterpret_cast<uint32_t*>(blob + o_err);
     // rounded up so the device-side bound stays an upper bound (and non-finite weights force the
     // full softmax)
     d.pi_bspread = std::isfinite(pi_bmax - pi_bmin) ? (pi_bmax - pi_bmin) * 1.001f + 1e-3f : INFINITY;
     d.pi_wmax = std::isfinite(pi_wmax) ? pi_wmax * 1.001f + 1e-3f : INFINITY;
-    *out = net;
+    *out = net.release();
     return YK_OK;
 }
 
@@ -299,8 +290,6 @@ int yk_net_errors(yk_net_t* net, uint32_t* flags) {
 }
 
 int yk_net_destroy(yk_net_t* net) {
-    if (!net) return YK_OK;
-    (void)hipFree(net->blob);
     delete net;
     return YK_OK;
 }

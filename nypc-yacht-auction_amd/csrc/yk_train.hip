@@ -533,7 +533,7 @@ struct yk_trainer {
     std::vector<long> off;  // tensor offsets, state_dict order
     std::vector<long> len;
     uint64_t step = 0;
-    std::vector<void*> allocs;
+    DeviceBlocks mem;
     // activations (Bmax rows)
     float *X = nullptr, *vt = nullptr, *vout = nullptr;
     int32_t* tgt = nullptr;
@@ -562,6 +562,10 @@ struct yk_trainer {
     double host_loss[3] = {0, 0, 0};
     int64_t row_base = 0;        // global row of the next backward's first example (dropout)
     yk::AmpTrain* amp = nullptr;  // mixed-precision mode (yk_train_amp.hip)
+    yk_trainer() = default;
+    yk_trainer(const yk_trainer&) = delete;
+    yk_trainer& operator=(const yk_trainer&) = delete;
+    ~yk_trainer() { yk::amp_destroy(amp); }
 };
 
 namespace {
@@ -569,18 +573,6 @@ namespace {
 enum { T_WIN = 0, T_BIN, T_GIN, T_BEIN };
 inline int t_blk(int b, int k) { return 4 + 8 * b + k; }  // k: 0 fc1.w 1 fc1.b 2 ln1.w 3 ln1.b 4 fc2.w 5 fc2.b 6 ln2.w 7 ln2.b
 inline int t_head(int NB, int k) { return 4 + 8 * NB + k; }  // 0 pi.0.w 1 pi.0.b 2 pi.2.w 3 pi.2.b 4 v.0.w 5 v.0.b 6 v.2.w 7 v.2.b 8 v.4.w 9 v.4.b
-
-template <class T>
-int talloc(yk_trainer* t, T** p, size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        clear_hip_error();
-        return YK_ERR_NOMEM;
-    }
-    t->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return YK_OK;
-}
 
 // row-major C[M][N] = op(A)[M][K] . op(B)[K][N] (+ beta C), op = transpose when ta / tb (A stored
 // [K][M], B stored [N][K]).  64 x 64 output tiles per 256-thread workgroup, each wave a 32 x 32
@@ -823,23 +815,12 @@ int yk_trainer_create(yk_trainer_t** out, int H, int NB, const float* const* par
     if (!(H == 64 || H == 128 || H == 256 || H == 512) || NB < 0 || NB > 64) return YK_ERR_ARG;
     if (nparams != 14 + 8 * NB || cfg->max_batch <= 0) return YK_ERR_ARG;
     if (!(cfg->dropout >= 0.0f && cfg->dropout < 1.0f)) return YK_ERR_ARG;
-    if (cfg->amp) {
-        // the mixed-precision step casts the Linear weights to fp16 (autocast): a finite weight with
-        // |w| >= 65520 becomes inf there - every step's loss non-finite, every GradScaler step skipped
-        // (torch's autocast path stalls the same way, silently); refused up front instead
-        auto out_of_range = [](const float* w, long len) {
-            for (long i = 0; i < len; i++)
-                if (std::isfinite(w[i]) && std::fabs(w[i]) >= 65520.f) return true;
-            return false;
-        };
-        if (out_of_range(params[0], (long)H * FEAT) || out_of_range(params[6 + 8 * NB], (long)ASIZE * H) ||
-            out_of_range(params[10 + 8 * NB], 128L * H))
-            return YK_ERR_RANGE;
-        for (int b = 0; b < NB; b++)
-            if (out_of_range(params[4 + 8 * b], (long)H * H) || out_of_range(params[8 + 8 * b], (long)H * H))
-                return YK_ERR_RANGE;
-    }
-    yk_trainer* t = new yk_trainer();
+    // the mixed-precision step casts the Linear weights to fp16 (autocast): a finite weight with
+    // |w| >= 65520 becomes inf there - every step's loss non-finite, every GradScaler step skipped
+    // (torch's autocast path stalls the same way, silently); refused up front instead
+    if (cfg->amp && !matrices_fit_fp16(params, H, NB)) return YK_ERR_RANGE;
+    std::unique_ptr<yk_trainer> owner(new yk_trainer());  // (until *out is set: every return before frees it)
+    yk_trainer* t = owner.get();
     t->H = H;
     t->NB = NB;
     t->Bmax = cfg->max_batch;
@@ -858,9 +839,7 @@ int yk_trainer_create(yk_trainer_t** out, int H, int NB, const float* const* par
     }
     t->nparams = o;
     const size_t Bm = (size_t)t->Bmax, HH = (size_t)H;
-    int rc = YK_OK;
-#define TA(p, c) \
-    if (rc == YK_OK) rc = talloc(t, &(p), (c))
+#define TA(p, c) YK_TRY(t->mem.alloc(&(p), (c)))
     TA(t->P, o);
     TA(t->G, o);
     TA(t->M, o);
@@ -915,7 +894,7 @@ int yk_trainer_create(yk_trainer_t** out, int H, int NB, const float* const* par
     TA(t->eloss, 2);
     // the column-sum jobs: (row buffer, gradient tensor, width)
     std::vector<ColJob> jobs;
-    if (rc == YK_OK) {
+    {
         auto G = [&](int k) { return t->G + t->off[k]; };
         jobs.push_back({t->dlogits, G(t_head(NB, 3)), ASIZE});
         jobs.push_back({t->dZv1, G(t_head(NB, 7)), 128});
@@ -944,45 +923,27 @@ int yk_trainer_create(yk_trainer_t** out, int H, int NB, const float* const* par
     t->ntiles = (int)tiles.size();
     TA(t->jobs, jobs.size());
     TA(t->tiles, tiles.size());
-    if (rc == YK_OK) {
-        (void)hipMemcpy(t->jobs, jobs.data(), sizeof(ColJob) * jobs.size(), hipMemcpyHostToDevice);
-        (void)hipMemcpy(t->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice);
-    }
 #undef TA
-    if (rc != YK_OK) {
-        yk_trainer_destroy(t);
-        return rc;
-    }
+    YK_HIP(hipMemcpy(t->jobs, jobs.data(), sizeof(ColJob) * jobs.size(), hipMemcpyHostToDevice));
+    YK_HIP(hipMemcpy(t->tiles, tiles.data(), sizeof(int2) * tiles.size(), hipMemcpyHostToDevice));
     for (size_t k = 0; k < n.size(); k++)
-        if (hipMemcpy(t->P + t->off[k], params[k], sizeof(float) * t->len[k], hipMemcpyHostToDevice) != hipSuccess) {
-            yk_trainer_destroy(t);
-            return YK_ERR_HIP;
-        }
-    (void)hipMemset(t->M, 0, sizeof(float) * o);
-    (void)hipMemset(t->V, 0, sizeof(float) * o);
-    (void)hipMemset(t->G, 0, sizeof(float) * o);
-    (void)hipMemset(t->acc, 0, sizeof(double) * 3);
-    (void)hipMemset(t->lsum, 0, sizeof(float) * 2);
+        YK_HIP(hipMemcpy(t->P + t->off[k], params[k], sizeof(float) * t->len[k], hipMemcpyHostToDevice));
+    YK_HIP(hipMemset(t->M, 0, sizeof(float) * o));
+    YK_HIP(hipMemset(t->V, 0, sizeof(float) * o));
+    YK_HIP(hipMemset(t->G, 0, sizeof(float) * o));
+    YK_HIP(hipMemset(t->acc, 0, sizeof(double) * 3));
+    YK_HIP(hipMemset(t->lsum, 0, sizeof(float) * 2));
     if (cfg->amp) {
-        if ((rc = yk::amp_create(&t->amp, H, NB, t->Bmax, t->P, t->G, t->off.data(), cfg->init_scale,
-                                 cfg->growth_interval)) != YK_OK ||
-            (rc = yk::amp_pack(t->amp, 0)) != YK_OK) {
-            yk_trainer_destroy(t);
-            return rc;
-        }
+        YK_TRY(yk::amp_create(&t->amp, H, NB, t->Bmax, t->P, t->G, t->M, t->V, t->nparams, t->off.data(), t->lrow,
+                              t->lsum, cfg->init_scale, cfg->growth_interval));
+        YK_TRY(yk::amp_pack(t->amp, 0));
     }
-    if (hipDeviceSynchronize() != hipSuccess) {
-        yk_trainer_destroy(t);
-        return YK_ERR_HIP;
-    }
-    *out = t;
+    YK_HIP(hipDeviceSynchronize());
+    *out = owner.release();
     return YK_OK;
 }
 
 int yk_trainer_destroy(yk_trainer_t* t) {
-    if (!t) return YK_OK;
-    yk::amp_destroy(t->amp);
-    for (void* p : t->allocs) (void)hipFree(p);
     delete t;
     return YK_OK;
 }
@@ -1000,7 +961,7 @@ static int backward_impl(yk_trainer_t* t, const yk_state_t* states, const int32_
                          const float* values, const int32_t* batch_idx, int batch, bool fuse_norm, hipStream_t s) {
     if (t->amp)
         return yk::amp_backward(t->amp, states, targets, soft, values, batch_idx, batch, t->cfg.dropout, t->cfg.seed,
-                                t->step, t->row_base, t->cfg.vloss_weight, t->lrow, t->lsum, fuse_norm, s);
+                                t->step, t->row_base, t->cfg.vloss_weight, fuse_norm, s);
     switch (t->H) {
         case 64: return step_impl<1>(t, states, targets, soft, values, batch_idx, batch, s);
         case 128: return step_impl<2>(t, states, targets, soft, values, batch_idx, batch, s);
@@ -1067,9 +1028,8 @@ int yk_trainer_apply(yk_trainer_t* t, void* stream) {
     hipStream_t s = as_stream(stream);
     t->step += 1;  // (amp: the dropout stream's step; the optimiser's count of steps taken is on the device)
     if (t->amp)
-        return yk::amp_apply(t->amp, t->nparams, t->M, t->V, t->acc + 2, t->cfg.max_grad_norm, t->cfg.lr,
-                             t->cfg.weight_decay, t->cfg.beta1, t->cfg.beta2, t->cfg.eps, t->cfg.dropout, t->cfg.seed,
-                             t->step, s);
+        return yk::amp_apply(t->amp, t->acc + 2, t->cfg.max_grad_norm, t->cfg.lr, t->cfg.weight_decay, t->cfg.beta1,
+                             t->cfg.beta2, t->cfg.eps, t->cfg.dropout, t->cfg.seed, t->step, s);
     const double b1 = t->cfg.beta1, b2 = t->cfg.beta2, st = (double)t->step;
     const double bc1 = 1.0 - std::pow(b1, st), bc2 = 1.0 - std::pow(b2, st);
     const float step_size = (float)(t->cfg.lr / bc1), bc2_sqrt = (float)std::sqrt(bc2);

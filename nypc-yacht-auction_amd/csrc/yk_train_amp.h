@@ -40,10 +40,11 @@ __device__ __forceinline__ float soft_row_sum(const SoftCsr& c, int64_t a0, int6
     return s;
 }
 
-// P / G: the trainer's flat f32 parameter and gradient buffers in YachtNNet.state_dict() order,
-// off[k]: offset of tensor k.  init_scale / growth_interval: GradScaler('cuda') (65536, 2000).
-int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, const long* off, float init_scale,
-               int growth_interval);
+// P / G / M / V: the trainer's flat f32 parameter, gradient and AdamW moment buffers (nparams each) in
+// YachtNNet.state_dict() order, off[k]: offset of tensor k.  lrow / lsum: the trainer's per-row losses
+// [Bmax] and their two column sums.  init_scale / growth_interval: GradScaler('cuda') (65536, 2000).
+int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, float* M, float* V, long nparams,
+               const long* off, float2* lrow, float* lsum, float init_scale, int growth_interval);
 void amp_destroy(AmpTrain* a);
 // fp16 copies of every weight matrix (both MFMA operand orientations) from P
 int amp_pack(AmpTrain* a, hipStream_t s);
@@ -56,13 +57,13 @@ int amp_pack(AmpTrain* a, hipStream_t s);
 // or null for the hard labels.
 int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
                  const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
-                 float vloss_weight, float2* lrow, float* lsum, bool fuse_norm, hipStream_t s);
+                 float vloss_weight, bool fuse_norm, hipStream_t s);
 // GradScaler.unscale_ + clip_grad_norm_(max_norm) + AdamW step (skipped, with the scale halved,
 // when a gradient is inf / nan) + GradScaler.update + fp16 repack.  sq_out: the unscaled grad
 // sq-norm (double).  dropout / seed / next_step: the next backward's dropout draws, which the
 // update launch makes ahead (for row offset 0) so that backward needs no mask launch of its own.
-int amp_apply(AmpTrain* a, long nparams, float* M, float* V, double* sq_out, float max_norm, float lr, float wd,
-              float b1, float b2, float eps, float dropout, uint64_t seed, uint64_t next_step, hipStream_t s);
+int amp_apply(AmpTrain* a, double* sq_out, float max_norm, float lr, float wd, float b1, float b2, float eps,
+              float dropout, uint64_t seed, uint64_t next_step, hipStream_t s);
 // HOST out[4]: loss scale, growth tracker, optimiser steps taken, whether the last step found inf
 int amp_state(AmpTrain* a, double* out);
 int amp_set_steps(AmpTrain* a, int64_t steps);

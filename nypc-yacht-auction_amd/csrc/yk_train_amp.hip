@@ -61,21 +61,13 @@ constexpr int TRPW = TRV / TW;  // rows per wave in the row passes
 constexpr int LDL = 3264;       // logits row stride: 204 tiles of 16 columns
 constexpr int PT = LDL / 16;    // policy column tiles
 constexpr int PKS = LDL / 32;   // 32-deep action slices
-#ifndef YK_HQ
-#define YK_HQ 8
-#endif
-#ifndef YK_BQ
-#define YK_BQ 12
-#endif
-constexpr int HQ = YK_HQ;       // policy-head column parts per row tile (+1 part: v_head.2)
-constexpr int BQ = YK_BQ;       // head-backward action parts per row tile (12: 6 -> 12 took the step
+constexpr int HQ = 8;           // policy-head column parts per row tile (+1 part: v_head.2)
+constexpr int BQ = 12;          // head-backward action parts per row tile (12: 6 -> 12 took the step
                                 // 102.5 -> 99.0 us at batch 64, +-0 at 512; 16 and 24 slower at 512,
                                 // profiles/r05ze_head_parts_trainab.log)
 constexpr int VH = 128;         // v_head hidden width
 constexpr int SQ_BLOCKS = 1024;
-#ifndef YK_DW_KG
-#define YK_DW_KG 2  // column tiles per trunk dW item
-#endif
+constexpr int DW_KG = 2;  // column tiles per trunk dW item
 
 struct Scaler {  // GradScaler('cuda') state + the AdamW step count (device)
     float scale;
@@ -988,72 +980,47 @@ struct DwJob {
 // norm: returns the item's sum of (g / scale)^2 over what it writes, in every lane (yk_trainer_step's
 // fused gradient norm: the grads k_amp_sq would read, summed where they are made); else 0
 __device__ __forceinline__ double wave_dsum(double x) { return xlane_sum(x); }
-#ifndef AMP_DW_SPLIT
-#define AMP_DW_SPLIT 1  // waves per trunk dW item in k_amp_grads (2, 4: the batch's slices split; slower, r06p)
-#endif
-#ifndef AMP_VS_PAIRS
-#define AMP_VS_PAIRS 4  // row pairs per batch of a column sum's loads (8, 16: within 0.3 us, r06r)
-#endif
-#ifndef AMP_DW_CH
+constexpr int VS_PAIRS = 4;  // row pairs per batch of a column sum's loads (8, 16: within 0.3 us, r06r)
 // slices whose fragments a dW item loads at once: 8 (AMP step at batch 512 111.9 -> 109.5 us; 4: 110.2,
 // 2: 112.2; at batch 64 8 costs 1 us over 4 - the reference trains at 512; profiles/r06q_dw_chunk_trainab.log)
-#define AMP_DW_CH 8
-#endif
-constexpr int DW_IPB = 4 / AMP_DW_SPLIT;  // trunk dW items per 4-wave k_amp_grads block
-// one dW item over S waves of the block (S = AMP_DW_SPLIT in k_amp_grads): wave part p sums slices
-// [p rsn / S, (p + 1) rsn / S), AMP_DW_CH slices' fragments loaded at once (global loads, unconditional:
-// past the part's last slice they re-read it), the MFMAs in slice order; part 0 adds
-// the others' accumulators in part order (through LDS) and stores.  Every wave of the block calls it
-// (has: whether its item exists), for the barrier.
-template <int NK, int S = AMP_DW_SPLIT>
-__device__ __forceinline__ double dw_item_split(const DwJob& jb, bool has, int nt, int kt0, int RS, int rsn, int lane,
-                                                int part, bool norm, float inv, float* red, int wave) {
-    constexpr int CH = AMP_DW_CH;
+constexpr int DW_CH = 8;
+// trunk dW items per 4-wave k_amp_grads block: a wave each (2 or 4 waves per item, the batch's slices
+// split between them, were slower, r06p)
+constexpr int DW_IPB = 4;
+// the item (16-row tile nt of jb's matrix, NK column tiles from kt0), where it exists (has): DW_CH slices'
+// fragments loaded at once (global loads, unconditional: past the last slice they re-read it), the MFMAs
+// in slice order
+template <int NK>
+__device__ __forceinline__ double dw_item(const DwJob& jb, bool has, int nt, int kt0, int RS, int rsn, int lane,
+                                          bool norm, float inv) {
+    constexpr int CH = DW_CH;
     floatx4 acc[NK];
 #pragma unroll
     for (int t = 0; t < NK; t++) acc[t] = zero4();
-    const int lo = part * rsn / S, hi = (part + 1) * rsn / S;
-    if (has && hi > lo) {
+    if (has && rsn > 0) {
         const float4* A = jb.A + (long)nt * RS * 64 + lane;
         const float4* X[NK];
 #pragma unroll
         for (int t = 0; t < NK; t++) X[t] = jb.X + (long)(kt0 + t) * RS * 64 + lane;
-        for (int r0 = lo; r0 < hi; r0 += CH) {
+        for (int r0 = 0; r0 < rsn; r0 += CH) {
             float4 a[CH], x[CH][NK];
 #pragma unroll
             for (int p = 0; p < CH; p++) {
-                const int s0 = min(r0 + p, hi - 1);
+                const int s0 = min(r0 + p, rsn - 1);
                 a[p] = gld4(A + (long)s0 * 64);
 #pragma unroll
                 for (int t = 0; t < NK; t++) x[p][t] = gld4(X[t] + (long)s0 * 64);
             }
 #pragma unroll
             for (int p = 0; p < CH; p++)
-                if (r0 + p < hi) {
+                if (r0 + p < rsn) {
 #pragma unroll
                     for (int t = 0; t < NK; t++) acc[t] = mfma(a[p], x[p][t], acc[t]);
                 }
         }
     }
-    if (S > 1) {
-        if (part > 0) {
-#pragma unroll
-            for (int t = 0; t < NK; t++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) red[((wave * 4 + t) * 4 + j) * 64 + lane] = acc[t][j];
-        }
-        __syncthreads();
-        if (part == 0) {
-#pragma unroll
-            for (int q = 1; q < S; q++)
-#pragma unroll
-                for (int t = 0; t < NK; t++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) acc[t][j] += red[(((wave + q) * 4 + t) * 4 + j) * 64 + lane];
-        }
-    }
     double ss = 0.0;
-    if (has && part == 0) {
+    if (has) {
         const int q = lane >> 4, c = lane & 15;
 #pragma unroll
         for (int t = 0; t < NK; t++) {
@@ -1072,15 +1039,15 @@ __device__ __forceinline__ double dw_item_split(const DwJob& jb, bool has, int n
     }
     return norm ? wave_dsum(ss) : 0.0;
 }
-// one weight-gradient item for one wave (the heads' items inside k_amp_bwd): the chunked form, unsplit
-__device__ __forceinline__ double dw_item(const DwJob* __restrict__ jobs, const int4 it, int RS, int rsn, int lane,
-                                          bool norm = false, float inv = 1.f) {
+// a heads' item (inside k_amp_bwd): any number of column tiles
+__device__ __forceinline__ double dw_item_heads(const DwJob* __restrict__ jobs, const int4 it, int RS, int rsn, int lane,
+                                                bool norm, float inv) {
     const DwJob jb = jobs[it.x];
     switch (it.w) {  // (uniform: the item's column tiles; amp_create's kg 2 or 4 divides every job's)
-        case 1: return dw_item_split<1, 1>(jb, true, it.y, it.z, RS, rsn, lane, 0, norm, inv, nullptr, 0);
-        case 2: return dw_item_split<2, 1>(jb, true, it.y, it.z, RS, rsn, lane, 0, norm, inv, nullptr, 0);
-        case 3: return dw_item_split<3, 1>(jb, true, it.y, it.z, RS, rsn, lane, 0, norm, inv, nullptr, 0);
-        default: return dw_item_split<4, 1>(jb, true, it.y, it.z, RS, rsn, lane, 0, norm, inv, nullptr, 0);
+        case 1: return dw_item<1>(jb, true, it.y, it.z, RS, rsn, lane, norm, inv);
+        case 2: return dw_item<2>(jb, true, it.y, it.z, RS, rsn, lane, norm, inv);
+        case 3: return dw_item<3>(jb, true, it.y, it.z, RS, rsn, lane, norm, inv);
+        default: return dw_item<4>(jb, true, it.y, it.z, RS, rsn, lane, norm, inv);
     }
 }
 // a block's waves' norm partials -> sqp[slot] (wave order: fixed bits); every thread calls it
@@ -1166,7 +1133,7 @@ __global__ __launch_bounds__(TTHR) void k_amp_bwd(AmpDev d, int B, float p, uint
                       // done before this launch), on the CUs the trunk's 8-row workgroups leave idle
         const int hb = tile - (B + TRV - 1) / TRV, w = hb * TW + wave;
         double ss = 0.0;
-        if (w < nhitems) ss = dw_item(jobs, hitems[w], d.RS, rsn, lane, sqp != nullptr, sqp ? 1.0f / d.sc->scale : 1.f);
+        if (w < nhitems) ss = dw_item_heads(jobs, hitems[w], d.RS, rsn, lane, sqp != nullptr, sqp ? 1.0f / d.sc->scale : 1.f);
         if (sqp) block_norm<TW>(ss, sqp, slot0 + hb);
         return;
     }
@@ -1419,7 +1386,7 @@ __device__ __forceinline__ void vecsum_item(const VsJob* __restrict__ jobs, cons
         int r = g;
         // per-example jobs (B rows): 2 VSP loads in flight per batch, added in the same order (a0: rows
         // g, g + 32, ..; a1: g + 16, g + 48, ..) as the one-pair loop below
-        constexpr int VSP = AMP_VS_PAIRS;
+        constexpr int VSP = VS_PAIRS;
         for (; r + 16 + 32 * (VSP - 1) < rows; r += 32 * VSP) {
             float v[2 * VSP];
 #pragma unroll
@@ -1469,27 +1436,20 @@ __global__ __launch_bounds__(256) void k_amp_grads(const DwJob* __restrict__ job
                                                    int nhtiles, int B, double* __restrict__ sqp, int nall,
                                                    const Scaler* __restrict__ sc) {
     __shared__ float part[16][17];
-    __shared__ float red[AMP_DW_SPLIT > 1 ? 4 * 4 * 4 * 64 : 1];  // the split dW items' partial accumulators
     const float inv = sqp ? 1.0f / sc->scale : 1.f;
     const int ndb = (nitems + DW_IPB - 1) / DW_IPB;
     if ((int)blockIdx.x >= ndb) {
         const int v = (int)blockIdx.x - ndb;
-#ifndef AMP_DIAG_NO_VS
         if (v < nvitems) vecsum_item(vjobs, vitems[v], ntiles, nhtiles, B, part, sqp, nall + v, inv);
-#endif
     } else {
         const int wave = threadIdx.x >> 6;
-        const int w = blockIdx.x * DW_IPB + wave / AMP_DW_SPLIT;
-        double ss = 0.0;
-#ifndef AMP_DIAG_NO_DW
+        const int w = blockIdx.x * DW_IPB + wave;
         const bool has = w < nitems;
         const int4 it = items[has ? w : 0];
         const DwJob jb = jobs[it.x];
-        // (every trunk item has YK_DW_KG column tiles: amp_create builds them so, and every trunk
+        // (every trunk item has DW_KG column tiles: amp_create builds them so, and every trunk
         // matrix's column-tile count, H / 16 or 4 for the input layer, is a multiple of it)
-        ss = dw_item_split<YK_DW_KG>(jb, has, it.y, it.z, RS, rsn, threadIdx.x & 63, wave % AMP_DW_SPLIT, sqp != nullptr,
-                                     inv, red, wave);
-#endif
+        const double ss = dw_item<DW_KG>(jb, has, it.y, it.z, RS, rsn, threadIdx.x & 63, sqp != nullptr, inv);
         if (sqp) block_norm<4>(ss, sqp, blockIdx.x);
     }
 }
@@ -1747,15 +1707,14 @@ namespace yk {
 struct AmpTrain {
     int H = 0, NB = 0, Bmax = 0, RS = 0, TMAX = 0;
     AmpDev d{};
-    std::vector<void*> allocs;
+    DeviceBlocks mem;
+    long nparams = 0;
     long* off_dev = nullptr;
     DwJob* dw_jobs = nullptr;
     int4* dw_items = nullptr;
     int n_dw_items = 0;
     int n_dw_trunk = 0;  // items [0, n_dw_trunk): k_amp_grads; the rest (the heads'): inside k_amp_bwd
     int n_norm_dw = 0;   // the fused norm's slots of the dW blocks (k_amp_grads' 4-wave, k_amp_bwd's TW-wave)
-    std::vector<int4> dw_items_host;
-    std::vector<int> dw_job_rows;  // for each item: unused (all jobs span the batch)
     VsJob* vs_jobs = nullptr;
     int2* vs_items = nullptr;
     int n_vs_items = 0;
@@ -1777,36 +1736,20 @@ struct AmpTrain {
     UpdJob* upd_jobs = nullptr;
     UpdItem* upd_items = nullptr;
     int n_upd_items = 0;
-    const float *upd_M = nullptr, *upd_V = nullptr;  // the moment buffers the jobs were built for
-    const long* off_host = nullptr;                    // (amp_create's offsets, kept for the jobs)
-    std::vector<long> offs;
-    float4 *win_f = nullptr, *w1f = nullptr, *w2f = nullptr, *w1t = nullptr, *w2t = nullptr, *wpif = nullptr,
-           *wpit = nullptr, *wv1f = nullptr, *wv1t = nullptr;
-    float* lsum_src_dummy = nullptr;
-    float2* lrow = nullptr;
-    float* lsum = nullptr;
+    float2* lrow = nullptr;   // the trainer's per-row losses (k_amp_headbwd writes them)
     float* psum = nullptr;    // soft targets: [Bmax] each batch row's sum of probabilities (soft_row_prep)
     int64_t* pcut = nullptr;  // [Bmax][BQ + 1] the CSR positions where the head-backward parts' runs begin
 };
 
-namespace {
-template <class T>
-int aalloc(AmpTrain* a, T** p, size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        clear_hip_error();
-        return YK_ERR_NOMEM;
-    }
-    a->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return YK_OK;
-}
-}  // namespace
+static int build_update_jobs(AmpTrain* a, const long* off, float* M, float* V);
 
-int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, const long* off, float init_scale,
-               int growth_interval) {
+int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, float* M, float* V, long nparams,
+               const long* off, float2* lrow, float* lsum, float init_scale, int growth_interval) {
     if (!(H == 64 || H == 128 || H == 256 || H == 512)) return YK_ERR_ARG;
-    AmpTrain* a = new AmpTrain();
+    std::unique_ptr<AmpTrain> owner(new AmpTrain());  // (until *out is set: every return before frees it)
+    AmpTrain* a = owner.get();
+    a->nparams = nparams;
+    a->lrow = lrow;
     a->H = H;
     a->NB = NB;
     a->Bmax = Bmax;
@@ -1824,26 +1767,18 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     const int ntens = 14 + 8 * NB;
     const size_t HH = (size_t)H * H, RS = (size_t)a->RS, Bm = (size_t)Bmax, T = (size_t)a->TMAX;
     const size_t tlH = (size_t)(H / 16) * RS * 512;  // halves of one T-layout [32 RS][H] matrix
-    int rc = YK_OK;
-#define AA(p, n) \
-    if (rc == YK_OK) rc = aalloc(a, &(p), (n))
+#define AA(p, n) YK_TRY(a->mem.alloc(&(p), (n)))
     AA(a->off_dev, (size_t)ntens);
     // fp16 weight fragments (float4 = 8 halves)
-    float4 *win_f = nullptr, *w1f = nullptr, *w2f = nullptr, *w1t = nullptr, *w2t = nullptr, *wpif = nullptr,
-           *wpit = nullptr, *wv1f = nullptr, *wv1t = nullptr;
-    AA(win_f, (size_t)H * 64 / 8);
-    AA(w1f, NB * HH / 8 + 1);
-    AA(w2f, NB * HH / 8 + 1);
-    AA(w1t, NB * HH / 8 + 1);
-    AA(w2t, NB * HH / 8 + 1);
-    AA(wpif, (size_t)LDL * H / 8);
-    AA(wpit, (size_t)LDL * H / 8);
-    AA(wv1f, (size_t)VH * H / 8);
-    AA(wv1t, (size_t)VH * H / 8);
-    d.win_f = win_f; d.w1f = w1f; d.w2f = w2f; d.w1t = w1t; d.w2t = w2t;
-    d.wpif = wpif; d.wpit = wpit; d.wv1f = wv1f; d.wv1t = wv1t;
-    a->win_f = win_f; a->w1f = w1f; a->w2f = w2f; a->w1t = w1t; a->w2t = w2t;
-    a->wpif = wpif; a->wpit = wpit; a->wv1f = wv1f; a->wv1t = wv1t;
+    AA(d.win_f, (size_t)H * 64 / 8);
+    AA(d.w1f, NB * HH / 8 + 1);
+    AA(d.w2f, NB * HH / 8 + 1);
+    AA(d.w1t, NB * HH / 8 + 1);
+    AA(d.w2t, NB * HH / 8 + 1);
+    AA(d.wpif, (size_t)LDL * H / 8);
+    AA(d.wpit, (size_t)LDL * H / 8);
+    AA(d.wv1f, (size_t)VH * H / 8);
+    AA(d.wv1t, (size_t)VH * H / 8);
     AA(d.xT, (size_t)4 * RS * 512);
     AA(d.hT, NB * tlH + 1);
     AA(d.r1T, NB * tlH + 1);
@@ -1877,20 +1812,11 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     AA(a->sqpart, (size_t)SQ_BLOCKS);
     AA(a->sc, 1);
     AA(a->sc_next, 1);
-    if (rc != YK_OK) {
-        amp_destroy(a);
-        return rc;
-    }
     for (int k = 0; k < ntens; k++)  // the kernels' closed-form offsets are the trainer's
-        if (poff(H, NB, k) != off[k]) {
-            amp_destroy(a);
-            return YK_ERR_ARG;
-        }
+        if (poff(H, NB, k) != off[k]) return YK_ERR_ARG;
     d.off = a->off_dev;
     d.sc = a->sc;
-    std::vector<long> offv(off, off + ntens);
-    a->offs = offv;
-    YK_HIP(hipMemcpy(a->off_dev, offv.data(), sizeof(long) * ntens, hipMemcpyHostToDevice));
+    YK_HIP(hipMemcpy(a->off_dev, off, sizeof(long) * ntens, hipMemcpyHostToDevice));
     Scaler s0{init_scale > 0.f ? init_scale : 65536.0f, 0, 0, 0, growth_interval > 0 ? growth_interval : 2000};
     YK_HIP(hipMemcpy(a->sc, &s0, sizeof(Scaler), hipMemcpyHostToDevice));
     // weight-gradient jobs: (dU T layout, X T layout, gradient, N, K)
@@ -1909,16 +1835,13 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     std::vector<int4> items;
     for (size_t j = 0; j < jobs.size(); j++) {
         const int ntn = (jobs[j].N + 15) / 16, ntk = (jobs[j].K + 15) / 16;
-        const int kg = (int)j < 1 + 2 * NB ? YK_DW_KG : 4;  // (k tiles per item: the trunk's fill more SIMDs with fewer)
+        const int kg = (int)j < 1 + 2 * NB ? DW_KG : 4;  // (k tiles per item: the trunk's fill more SIMDs with fewer)
         for (int k0 = 0; k0 < ntk; k0 += kg)
             for (int nt = 0; nt < ntn; nt++) items.push_back(make_int4((int)j, nt, k0, std::min(kg, ntk - k0)));
     }
     a->n_dw_items = (int)items.size();
-    for (const int4& it : items)  // (k_amp_grads runs the trunk's items as YK_DW_KG-tile items)
-        if (it.x < 1 + 2 * NB && it.w != YK_DW_KG) {
-            amp_destroy(a);
-            return YK_ERR_ARG;
-        }
+    for (const int4& it : items)  // (k_amp_grads runs the trunk's items as DW_KG-tile items)
+        if (it.x < 1 + 2 * NB && it.w != DW_KG) return YK_ERR_ARG;
     a->n_dw_trunk = 0;  // the items of the input layer's and the blocks' matrices come first
     while (a->n_dw_trunk < a->n_dw_items && items[a->n_dw_trunk].x < 1 + 2 * NB) a->n_dw_trunk++;
     a->n_norm_dw = (a->n_dw_trunk + DW_IPB - 1) / DW_IPB + (a->n_dw_items - a->n_dw_trunk + TW - 1) / TW;
@@ -1946,8 +1869,7 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     vj.push_back({d.dz1f, G + off[t_head(NB, HV_B1)], VH, VH, 1, 1, 1});
     vj.push_back({d.v2prod, G + off[t_head(NB, HV_W2)], VH, VH, 1, 1, 1});
     vj.push_back({d.dzv2, G + off[t_head(NB, HV_B2)], 1, 1, 1, 1, 1});
-    const size_t loss_job = vj.size();  // (the trainer's lrow / lsum: filled in per call)
-    vj.push_back({nullptr, nullptr, 2, 2, 1, 0, 0});
+    vj.push_back({reinterpret_cast<const float*>(lrow), lsum, 2, 2, 1, 0, 0});  // the batch's two loss sums
     std::vector<int2> vitems;
     for (size_t j = 0; j < vj.size(); j++)
         for (int c = 0; c < vj[j].N; c += 16) vitems.push_back(make_int2((int)j, c));
@@ -1955,57 +1877,48 @@ int amp_create(AmpTrain** out, int H, int NB, int Bmax, float* P, float* G, cons
     // fp16 pack jobs
     std::vector<PackJob> pj;
     long first = 0;
-    auto pack = [&](const float* W, float4* dst, int N, int K, int Np, int Kp, int trans) {
-        pj.push_back({W, dst, N, K, Np, Kp, trans, first});
+    auto pack = [&](const float* W, const float4* dst, int N, int K, int Np, int Kp, int trans) {
+        pj.push_back({W, const_cast<float4*>(dst), N, K, Np, Kp, trans, first});
         first += (long)Np * Kp / 8;
     };
-    pack(P + off[T_WIN], win_f, H, FEAT, H, 64, 0);
+    pack(P + off[T_WIN], d.win_f, H, FEAT, H, 64, 0);
     for (int b = 0; b < NB; b++) {
-        pack(P + off[t_blk(b, 0)], w1f + b * HH / 8, H, H, H, H, 0);
-        pack(P + off[t_blk(b, 4)], w2f + b * HH / 8, H, H, H, H, 0);
-        pack(P + off[t_blk(b, 0)], w1t + b * HH / 8, H, H, H, H, 1);
-        pack(P + off[t_blk(b, 4)], w2t + b * HH / 8, H, H, H, H, 1);
+        pack(P + off[t_blk(b, 0)], d.w1f + b * HH / 8, H, H, H, H, 0);
+        pack(P + off[t_blk(b, 4)], d.w2f + b * HH / 8, H, H, H, H, 0);
+        pack(P + off[t_blk(b, 0)], d.w1t + b * HH / 8, H, H, H, H, 1);
+        pack(P + off[t_blk(b, 4)], d.w2t + b * HH / 8, H, H, H, H, 1);
     }
-    pack(P + off[t_head(NB, HP_W)], wpif, ASIZE, H, LDL, H, 0);
-    pack(P + off[t_head(NB, HP_W)], wpit, ASIZE, H, H, LDL, 1);
-    pack(P + off[t_head(NB, HV_W1)], wv1f, VH, H, VH, H, 0);
-    pack(P + off[t_head(NB, HV_W1)], wv1t, VH, H, H, VH, 1);
+    pack(P + off[t_head(NB, HP_W)], d.wpif, ASIZE, H, LDL, H, 0);
+    pack(P + off[t_head(NB, HP_W)], d.wpit, ASIZE, H, H, LDL, 1);
+    pack(P + off[t_head(NB, HV_W1)], d.wv1f, VH, H, VH, H, 0);
+    pack(P + off[t_head(NB, HV_W1)], d.wv1t, VH, H, H, VH, 1);
     a->n_pk_jobs = (int)pj.size();
     a->pk_total = first;
     std::vector<uint8_t> pblk;
     for (size_t j = 0; j < pj.size(); j++) {
         const long n = (j + 1 < pj.size() ? pj[j + 1].first : first) - pj[j].first;
-        if (n % 256 != 0 || pj.size() > 255) {  // a block would straddle two jobs
-            amp_destroy(a);
-            return YK_ERR_ARG;
-        }
+        if (n % 256 != 0 || pj.size() > 255) return YK_ERR_ARG;  // a block would straddle two jobs
         pblk.insert(pblk.end(), (size_t)(n / 256), (uint8_t)j);
     }
-    if (aalloc(a, &a->dw_jobs, jobs.size()) || aalloc(a, &a->dw_items, items.size()) ||
-        aalloc(a, &a->vs_jobs, vj.size()) || aalloc(a, &a->vs_items, vitems.size()) ||
-        aalloc(a, &a->pk_jobs, pj.size()) || aalloc(a, &a->pk_blk, pblk.size()) ||
-        aalloc(a, &a->sq_items, (size_t)(a->n_dw_items + a->n_vs_items))) {  // (>= the blocks')
-        amp_destroy(a);
-        return YK_ERR_NOMEM;
-    }
+    AA(a->dw_jobs, jobs.size());
+    AA(a->dw_items, items.size());
+    AA(a->vs_jobs, vj.size());
+    AA(a->vs_items, vitems.size());
+    AA(a->pk_jobs, pj.size());
+    AA(a->pk_blk, pblk.size());
+    AA(a->sq_items, (size_t)(a->n_dw_items + a->n_vs_items));  // (>= the blocks')
     YK_HIP(hipMemcpy(a->dw_jobs, jobs.data(), sizeof(DwJob) * jobs.size(), hipMemcpyHostToDevice));
     YK_HIP(hipMemcpy(a->dw_items, items.data(), sizeof(int4) * items.size(), hipMemcpyHostToDevice));
     YK_HIP(hipMemcpy(a->vs_items, vitems.data(), sizeof(int2) * vitems.size(), hipMemcpyHostToDevice));
     YK_HIP(hipMemcpy(a->pk_jobs, pj.data(), sizeof(PackJob) * pj.size(), hipMemcpyHostToDevice));
     YK_HIP(hipMemcpy(a->pk_blk, pblk.data(), pblk.size(), hipMemcpyHostToDevice));
-    // the loss-sum job's buffers are the trainer's; amp_backward patches them in on first use
     YK_HIP(hipMemcpy(a->vs_jobs, vj.data(), sizeof(VsJob) * vj.size(), hipMemcpyHostToDevice));
-    a->lsum_src_dummy = nullptr;
-    (void)loss_job;
-    *out = a;
+    YK_TRY(build_update_jobs(a, off, M, V));
+    *out = owner.release();
     return YK_OK;
 }
 
-void amp_destroy(AmpTrain* a) {
-    if (!a) return;
-    for (void* p : a->allocs) (void)hipFree(p);
-    delete a;
-}
+void amp_destroy(AmpTrain* a) { delete a; }
 
 int amp_pack(AmpTrain* a, hipStream_t s) {
     hipLaunchKernelGGL(k_amp_pack, dim3((unsigned)((a->pk_total + 255) / 256)), dim3(256), 0, s, a->pk_jobs,
@@ -2016,7 +1929,7 @@ int amp_pack(AmpTrain* a, hipStream_t s) {
 
 int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
                  const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
-                 float vloss_weight, float2* lrow, float* lsum, bool fuse_norm, hipStream_t s) {
+                 float vloss_weight, bool fuse_norm, hipStream_t s) {
     if (B <= 0 || B > a->Bmax) return YK_ERR_ARG;
     a->norm_ready = false;
     SoftCsr sv{};  // the soft launches' argument: the caller's CSR and this trainer's per-row scratch
@@ -2027,13 +1940,6 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
     }
     double* sqp = fuse_norm ? a->sq_items : nullptr;
     AmpDev& d = a->d;
-    if (a->lrow != lrow || a->lsum != lsum) {  // the loss-sum job reads the trainer's row losses
-        const int j = 3 + 6 * a->NB + 4 + 4;
-        VsJob jb{reinterpret_cast<const float*>(lrow), lsum, 2, 2, 1, 0, 0};
-        YK_HIP(hipMemcpy(a->vs_jobs + j, &jb, sizeof(VsJob), hipMemcpyHostToDevice));
-        a->lrow = lrow;
-        a->lsum = lsum;
-    }
     // T: the heads' 16-row tiles; TT: the trunk's TRV-row workgroups
     const int T = (B + TR - 1) / TR, TT = (B + TRV - 1) / TRV, rsn = (B + 31) / 32;
     if (dropout > 0.f && !(a->mask_valid && a->mask_seed == seed && a->mask_step == step && a->mask_row_base == row_base &&
@@ -2056,10 +1962,10 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
         YK_LAUNCHED();                                                                                              \
         if (soft)                                                                                                   \
             hipLaunchKernelGGL((k_amp_headbwd<HH, true>), dim3(T, BQ + 1), dim3(TTHR), 0, s, d, sv, values, idx, B,  \
-                               vloss_weight, lrow);                                                                 \
+                               vloss_weight, a->lrow);                                                              \
         else                                                                                                        \
             hipLaunchKernelGGL(k_amp_headbwd<HH>, dim3(T, BQ + 1), dim3(TTHR), 0, s, d, targets, values, idx, B,   \
-                               vloss_weight, lrow);                                                                 \
+                               vloss_weight, a->lrow);                                                              \
         YK_LAUNCHED();                                                                                              \
         hipLaunchKernelGGL(k_amp_bwd<HH>, dim3(TT + (a->n_dw_items - a->n_dw_trunk + TW - 1) / TW), dim3(TTHR), 0, s, \
                            d, B, dropout, seed, step, row_base, a->dw_jobs, a->dw_items + a->n_dw_trunk,          \
@@ -2082,30 +1988,31 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
 }
 
 // k_amp_update's work list: a 32 x 32 tile of every packed weight matrix, and 1024-element slices
-// of the parameters no matrix covers
-static int build_update_jobs(AmpTrain* a, long nparams, float* M, float* V) {
+// of the parameters no matrix covers (M, V: the trainer's moment buffers)
+static int build_update_jobs(AmpTrain* a, const long* off, float* M, float* V) {
     const int H = a->H, NB = a->NB;
-    const long* off = a->offs.data();
+    const long nparams = a->nparams;
+    const AmpDev& d = a->d;
     const size_t HH = (size_t)H * H;
     float* P = const_cast<float*>(a->d.P);
     float* G = a->d.G;
     std::vector<UpdJob> jobs;
     std::vector<UpdItem> items;
     std::vector<std::pair<long, long>> mats;
-    auto mat = [&](long o, int N, int K, float4* dN, int KpN, float4* dT, int KpT) {
+    auto mat = [&](long o, int N, int K, const float4* dN, int KpN, const float4* dT, int KpT) {
         const int j = (int)jobs.size();
-        jobs.push_back({P + o, G + o, M + o, V + o, dN, dT, N, K, KpN, KpT});
+        jobs.push_back({P + o, G + o, M + o, V + o, const_cast<float4*>(dN), const_cast<float4*>(dT), N, K, KpN, KpT});
         for (int n0 = 0; n0 < N; n0 += 32)
             for (int k0 = 0; k0 < K; k0 += 32) items.push_back({j, n0, k0});
         mats.push_back({o, o + (long)N * K});
     };
-    mat(off[T_WIN], H, FEAT, a->win_f, 64, nullptr, 0);
+    mat(off[T_WIN], H, FEAT, d.win_f, 64, nullptr, 0);
     for (int b = 0; b < NB; b++) {
-        mat(off[t_blk(b, 0)], H, H, a->w1f + b * HH / 8, H, a->w1t + b * HH / 8, H);
-        mat(off[t_blk(b, 4)], H, H, a->w2f + b * HH / 8, H, a->w2t + b * HH / 8, H);
+        mat(off[t_blk(b, 0)], H, H, d.w1f + b * HH / 8, H, d.w1t + b * HH / 8, H);
+        mat(off[t_blk(b, 4)], H, H, d.w2f + b * HH / 8, H, d.w2t + b * HH / 8, H);
     }
-    mat(off[t_head(NB, HP_W)], ASIZE, H, a->wpif, H, a->wpit, LDL);
-    mat(off[t_head(NB, HV_W1)], VH, H, a->wv1f, H, a->wv1t, VH);
+    mat(off[t_head(NB, HP_W)], ASIZE, H, d.wpif, H, d.wpit, LDL);
+    mat(off[t_head(NB, HV_W1)], VH, H, d.wv1f, H, d.wv1t, VH);
     std::sort(mats.begin(), mats.end());
     const int jv = (int)jobs.size();
     jobs.push_back({P, G, M, V, nullptr, nullptr, 0, 0, 0, 0});
@@ -2115,26 +2022,20 @@ static int build_update_jobs(AmpTrain* a, long nparams, float* M, float* V) {
         for (long e = pos; e < m.first; e += 1024) items.push_back({jv, (int)e, (int)std::min<long>(1024, m.first - e)});
         pos = std::max(pos, m.second);
     }
-    if (!a->upd_jobs && (aalloc(a, &a->upd_jobs, jobs.size()) || aalloc(a, &a->upd_items, items.size())))
-        return YK_ERR_NOMEM;
+    YK_TRY(a->mem.alloc(&a->upd_jobs, jobs.size()));
+    YK_TRY(a->mem.alloc(&a->upd_items, items.size()));
     YK_HIP(hipMemcpy(a->upd_jobs, jobs.data(), sizeof(UpdJob) * jobs.size(), hipMemcpyHostToDevice));
     YK_HIP(hipMemcpy(a->upd_items, items.data(), sizeof(UpdItem) * items.size(), hipMemcpyHostToDevice));
     a->n_upd_items = (int)items.size();
-    a->upd_M = M;
-    a->upd_V = V;
     return YK_OK;
 }
 
-int amp_apply(AmpTrain* a, long nparams, float* M, float* V, double* sq_out, float max_norm, float lr, float wd,
-              float b1, float b2, float eps, float dropout, uint64_t seed, uint64_t next_step, hipStream_t s) {
-    if (a->upd_M != M || a->upd_V != V) {  // the update jobs address the trainer's moment buffers
-        const int rc = build_update_jobs(a, nparams, M, V);
-        if (rc != YK_OK) return rc;
-    }
+int amp_apply(AmpTrain* a, double* sq_out, float max_norm, float lr, float wd, float b1, float b2, float eps,
+              float dropout, uint64_t seed, uint64_t next_step, hipStream_t s) {
     const bool fused = a->norm_ready;  // (yk_trainer_step: k_amp_grads summed the norm; no all-reduce between)
     a->norm_ready = false;
     if (!fused) {
-        hipLaunchKernelGGL(k_amp_sq, dim3(SQ_BLOCKS), dim3(256), 0, s, a->d.G, nparams, a->sc, a->sqpart);
+        hipLaunchKernelGGL(k_amp_sq, dim3(SQ_BLOCKS), dim3(256), 0, s, a->d.G, a->nparams, a->sc, a->sqpart);
         YK_LAUNCHED();
     }
     const long nm = dropout > 0.f ? (long)(1 + a->NB) * a->Bmax * (a->H / 4) : 0;

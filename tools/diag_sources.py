@@ -107,7 +107,7 @@ int yk_diag_select(uint64_t* out, int n) {  // HOST out[n][16]; resets the accum
 # or the root's full scan), 2 step + canonical, 3 whole descent, 4 levels, 5 entries scanned, 6 expand
 # + backup, 8-10 expand phases, 12 backup, 13 the root's incremental scan (root_scan), 14 its entries
 ENGINE = [
-    (r"^constexpr uint32_t RV_OFF = .*\n", "after", ENGINE_GLOBALS),
+    (r"^// \(the node / edge records, EngDev, the error bits and the tree lookups: yk_engine_dev\.h\)\n", "after", ENGINE_GLOBALS),
     (r"^    PyV res\{0\.0, T_INT\};\n    // the root's pick", "before_line2", "    SEL_T0(t_all);\n"),
     (r"^        if \(rc\.x != 0 && rc1\.z != RV_OFF\) \{  // k_root_sort ran this move.*\n", "after", "            SEL_T0(t_rs);\n            const uint64_t sc0 = scanned;\n"),
     (r"^            pre = pre_bj != -1;\n", "after", "            SEL_ACC(13, t_rs);\n            SEL_ADD(14, scanned - sc0);\n"),
@@ -115,7 +115,7 @@ ENGINE = [
     (r"^        if \(V == 0\) \{  // no valid action: MCTS.py:141-147.*\n", "before", "        SEL_ACC(0, t_lv);\n        SEL_T0(t_sc);\n"),
     (r"^        const int bj = bj_out;\n", "after", "        SEL_ACC(1, t_sc);\n        SEL_ADD(4, 1);\n        SEL_ADD(5, V);\n        SEL_T0(t_st);\n"),
     (r"^        s = canonical\(s, np\);  // MCTS.py:150\n", "after", "        SEL_ACC(2, t_st);\n"),
-    (r"^        d\.gstats\[\(long\)e \* GST \+ 8\] \+= gathered;\n    \}\n\}\n", "before_last_brace", "    SEL_ACC(3, t_all);\n"),
+    (r"^        atomicAdd\(gs \+ 8, \(unsigned long long\)gathered\);\n    \}\n\}\n", "before_last_brace", "    SEL_ACC(3, t_all);\n"),
     (r"^    if \(d\.done\[e\]\) return;\n    expand_backup_game\(d, e, lane\);\n", "replace",
      "    if (d.done[e]) return;\n" + XSPAN_BEGIN + "    expand_backup_game(d, e, lane);\n" + XSPAN_MID),
     (r"^        select_game\(d, e, lane, env_ids, ctr_arr\);\n    \}\n\}\n\n__device__ __forceinline__ void expand_backup_game",
@@ -177,7 +177,7 @@ FWD = [
     # the prologue (slots 32-36, 38): static vectors in LDS, the weight loads issued, features
     # written, the input barrier, the input GEMM done, its barrier passed; block 0's tile-list build (39 -> 37)
     (r"^        reinterpret_cast<float4\*>\(VS\)\[tid \+ NTH \* k\] = vsv\[k\];.*\n", "after", "    TSTAMP(32);\n"),
-    (r"^    if \(tid < TMW\) UM\[tid\] = 0u;\n    if \(tid == 0\) VHC = 0u;\n    lds_barrier\(\);\n", "around", ("    TSTAMP(33);\n", "    TSTAMP(34);\n")),
+    (r"^    if \(tid < TMW\) UM\[tid\] = 0u;\n    if \(tid == 0\) \{\n        VHC = 0u;\n        SYNC_LOST = 0u;\n    \}\n    lds_barrier\(\);\n", "around", ("    TSTAMP(33);\n", "    TSTAMP(34);\n")),
     (r"^    __builtin_amdgcn_sched_barrier\(0\);  // the first layer streams in under the featurize / input phase\n", "after",
      "    TSTAMP(38);\n"),
     (r"^    lds_barrier\(\);  // T complete; every wave is done reading the feature planes\n", "around",
@@ -193,7 +193,7 @@ FWD = [
      ("        if (b == 2) LSTAMP(4);\n", "        if (b == 2) { LSTAMP(5); TSTAMP(18); }\n")),
     (r"^            else mma_ring<PL, H, NT, RW, N2, DEF, V>.*\n        \}\n", "after", "        if (b == 2) { LSTAMP(6); TSTAMP(19); }\n"),
     (r"^        lds_barrier\(\);  // T complete; every wave is done reading h's planes\n", "after", "        if (b == 2) TSTAMP(21);\n"),
-    (r"^        lds_barrier\(\);\n    \};\n    for \(int b = 0; b \+ 1 < net.NB", "after_line1", "        if (b < 6) TSTAMP(3 + b);\n"),
+    (r"^        lds_barrier\(\);\n    \};\n    // NB0 \(nblocks = 0, a separate instantiation", "after_line1", "        if (b < 6) TSTAMP(3 + b);\n"),
     (r"^    lds_barrier\(\);\n    // The policy head over all real tiles", "after_line1", "    TSTAMP(9);\n"),
     (r"^        for \(int t = 0; t < PC; t\+\+\) tcur\[t\] = tnxt\[t\];\n", "after",
      "        if (c == 1 || c == 3) TSTAMP(10 + (c >> 1));\n        if (c == 5) TSTAMP(12);\n"),
