@@ -406,19 +406,31 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
     return bj;
 }
 
-// One simulation's descent (MCTS.search, MCTS.py:56-152 up to the recursion).
-// All 64 lanes of the game's wave call it together.
-__device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, const uint32_t* env_ids, uint64_t* ctr_arr) {
-    if (d.done[e] || d.idle[e]) {
-        if (lane == 0) {
-            d.leaf_flag[e] = 0;
-            d.path_len[e] = 0;
-            d.end_node[e] = 0;
-        }
-        return;
+// A game without a descent this simulation (finished, or an arena seat that does not search)
+__device__ __forceinline__ void select_none(const EngDev& d, int e, int lane) {
+    if (lane == 0) {
+        d.leaf_flag[e] = 0;
+        d.path_len[e] = 0;
+        d.end_node[e] = 0;
     }
-    const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
-    const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
+}
+
+// One simulation's descent (MCTS.search, MCTS.py:56-152 up to the recursion) of a game that searches
+// (not done, not idle: the caller's test) in its tree t, generation g.  The caller passes t and g:
+// the fused kernel's expansion holds them already, and re-reading done / idle / tree_of / gen[t]
+// would put two more dependent round trips on every simulation's chain.
+// All 64 lanes of the game's wave call it together.
+//
+// Invariant (no node is terminal): the key of every node record is a state with game_ended == 0.
+// The one writer of a new record is the expansion of a leaf, and a descent flags a leaf only after
+// that state's Es test below came out 0; k_move_begin's compaction copies records unchanged, and the
+// external-root and dual-tree paths insert through the same expansion into the tree they search.
+// game_ended is a function of the state alone.  So a level whose node is already known - the cached
+// root (root_c: set after a lookup that followed the test) or a cached child (an edge tag: the backup
+// caches only ids of records, the next level's node, the new leaf or a node without valid actions;
+// after a terminal break end_id is 0 and nothing is cached) - needs no Es test and no lookup.
+__device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, int t, int g, const uint32_t* env_ids,
+                                            uint64_t* ctr_arr) {
     YkS s = ld_state(d.root + e);
     Stream rs{d.seed, env_ids[e], ctr_arr[e]};
     const NodeRec* nodes = d.nodes[g] + (long)t * d.NCAP;
@@ -430,19 +442,35 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
     uint64_t scanned = 0, gathered = 0;  // UCB entries read; their edges gathered (visited entries)
     int ngl = 0;                          // this lane's edge gathers in full scans
     int leaf = 0;
-    int known = -1;        // the node this level's state is, when the edge taken to it cached it
     uint32_t end_id = 0;   // id + 1 of a node the descent stops at
     PyV res{0.0, T_INT};
+    // this level's node when it is known before any lookup (the cached root, a cached child): its id
+    // and fields, fetched in one batch
+    bool have = false;
+    int nid = -1;
+    NodeF f{};
     // the root's pick from its P order and visited list (root_scan), made before the walk, where
     // little else is live (inside the loop the second scan path would spill)
     bool pre = false;
     int pre_bj = 0x7FFFFFFF;
     uint32_t pre_tag = 0;
     {
+        // the root is the same node for every simulation of a move: its id and the record's fixed
+        // fields are kept after the first lookup (root_c, read once per descent), which saves the
+        // hash, the index probe and the key's compare; Ns and first_j come from the record
         const uint4 rc = d.root_c[2 * t], rc1 = d.root_c[2 * t + 1];
-        if (rc.x != 0 && rc1.z != RV_OFF) {  // k_root_sort ran this move: root_c holds the root
-            const uint32_t Ns = nodes[rc.x - 1].Ns;
-            const float sq = (float)sqrt((double)Ns), sqe = (float)sqrt((double)Ns + 1e-8);
+        const uint32_t rid = uni(rc.x);
+        if (rid != 0) {
+            have = true;
+            nid = (int)rid - 1;
+            f = ld_node(nodes + nid);
+            f.p_off = rc.y;
+            f.nvalid = rc.z;
+            f.vinfo = (uint64_t)rc1.x | ((uint64_t)rc1.y << 32);
+            f = uniform(f);
+        }
+        if (rid != 0 && uni(rc1.z) != RV_OFF) {  // k_root_sort ran this move: root_c holds the root
+            const float sq = (float)sqrt((double)f.Ns), sqe = (float)sqrt((double)f.Ns + 1e-8);
             pre_bj = __builtin_amdgcn_readfirstlane(root_scan(d, t, lane, rc1.z, Pbase + rc.y, Sbase + rc.y, edges,
                                                               (int)rc.z, (int)rc.w, (int)rc1.w, sq, sqe, pre_tag, scanned,
                                                               gathered));
@@ -451,50 +479,38 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
         }
     }
     while (true) {
-        if (known >= 0) {  // the cached child: its key is the state step + canonical would give
-            const uint64_t* kp = nodes[known].key;
-#pragma unroll
-            for (int i = 0; i < 8; i++) s.w[i] = kp[i];
-        }
-        const double es = game_ended(s, 1);  // Es (MCTS.py:78-82)
-        if (es != 0.0) {
-            res = PyV{-es, T_F64};
-            break;
-        }
-        // the root (depth 0) is the same node for every simulation of a move: its id and the
-        // record's fixed fields are kept after the first lookup, which saves the hash, the index
-        // probe and the record's round trip before the prior / slot loads
-        uint4 rc0 = make_uint4(0, 0, 0, 0), rc1 = rc0;
-        if (depth == 0) {
-            rc0 = d.root_c[2 * t];
-            rc1 = d.root_c[2 * t + 1];
-        }
-        const bool cached = rc0.x != 0;
-        const uint64_t hsh = (cached || known >= 0) ? 0ull : index_hash(s);
-        const int nid = cached ? (int)rc0.x - 1 : known >= 0 ? known : lookup(d, g, t, s, hsh);
-        if (nid < 0) {  // leaf: predict (MCTS.py:84-115)
-            leaf = 1;
-            if (lane == 0) {
-                st_state(d.leaf_state + e, s);
-                d.leaf_hash[e] = hsh;
+        if (!have) {
+            const double es = game_ended(s, 1);  // Es (MCTS.py:78-82)
+            if (es != 0.0) {
+                res = PyV{-es, T_F64};
+                break;
             }
-            break;
+            const uint64_t hsh = index_hash(s);
+            nid = __builtin_amdgcn_readfirstlane(lookup(d, g, t, s, hsh, f));
+            f = uniform(f);
+            if (nid < 0) {  // leaf: predict (MCTS.py:84-115)
+                leaf = 1;
+                if (lane == 0) {
+                    st_state(d.leaf_state + e, s);
+                    d.leaf_hash[e] = hsh;
+                }
+                break;
+            }
+            if (depth == 0 && lane == 0) {  // the move's root, for its later descents
+                d.root_c[2 * t] = make_uint4((uint32_t)nid + 1, f.p_off, f.nvalid, 0);
+                d.root_c[2 * t + 1] = make_uint4((uint32_t)f.vinfo, (uint32_t)(f.vinfo >> 32), RV_OFF, 0);
+            }
         }
-        const NodeRec& nd = nodes[nid];
-        const uint32_t p_off = cached ? rc0.y : nd.p_off;
-        const int V = cached ? (int)rc0.z : (int)nd.nvalid;
-        const uint64_t vinfo = cached ? ((uint64_t)rc1.x | ((uint64_t)rc1.y << 32)) : nd.vinfo;
-        if (depth == 0 && !cached && lane == 0) {
-            d.root_c[2 * t] = make_uint4((uint32_t)nid + 1, p_off, (uint32_t)V, 0);
-            d.root_c[2 * t + 1] = make_uint4((uint32_t)vinfo, (uint32_t)(vinfo >> 32), RV_OFF, 0);
-        }
+        const uint32_t p_off = f.p_off;
+        const int V = (int)f.nvalid;
+        const uint64_t vinfo = f.vinfo;
         if (V == 0) {  // no valid action: MCTS.py:141-147 returns 0 (python int)
             res = PyV{0.0, T_INT};
             end_id = (uint32_t)nid + 1;
             break;
         }
         // UCB argmax, MCTS.py:117-135: float32 arithmetic, strict '>' => lowest action wins
-        const uint32_t Ns = nd.Ns;
+        const uint32_t Ns = f.Ns;
         // f32(sqrt(Ns)), f32(sqrt(Ns + 1e-8)) (MCTS.py:125-129 under NEP 50): f64 sqrt is correctly
         // rounded, so these are the bits numpy gets; computed here rather than read from a table,
         // which saves a dependent load per level (expand 53.35 -> 53.02 us, profiles/r03_expand_ab.log)
@@ -516,7 +532,7 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
             // seeds every lane and leaves the scan nothing to read (a second exit path here spills).
             int Vs = V;  // entries the full scan reads
             if (d.node_summary && Ns == 0) {
-                bj = (int)nd.first_j;
+                bj = (int)f.first_j;
                 Vs = 0;
             }
             // software-pipelined scan: iteration it+1's P / slot loads fly while iteration it's
@@ -574,14 +590,19 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, co
             res = PyV{0.0, T_INT};
             break;
         }
-        const uint32_t child = bj == 0x7FFFFFFF ? 0u : (wtag >> 2);  // id + 1, 0: not cached
+        const uint32_t child = uni(bj == 0x7FFFFFFF ? 0u : (wtag >> 2));  // id + 1, 0: not cached
         if (child) {  // a deterministic transition taken before: the child node is known
             if (lane == 0) path[depth] = ((uint64_t)(p_off + (uint32_t)j) << 32) | (uint32_t)nid | PATH_DET;
             depth++;
-            known = (int)child - 1;
+            // the whole record in one batch, the fields first; the key is the state step + canonical
+            // would give, which the next level needs only if it has to step
+            have = true;
+            nid = (int)child - 1;
+            f = uniform(ld_node(nodes + nid));
+            s = ld_state(reinterpret_cast<const yk_state_t*>(nodes[nid].key));
             continue;
         }
-        known = -1;
+        have = false;
         const VInfo vi = unpack_vinfo(vinfo, (uint32_t)V);
         const int a = compact_to_action(vi, j);
         int np = 1;
@@ -620,29 +641,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));
     if (e >= d.e_hi) return;
-    select_game(d, e, lane, env_ids, ctr_arr);
+    if (d.done[e] || d.idle[e]) {
+        select_none(d, e, lane);
+        return;
+    }
+    const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
+    const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
+    select_game(d, e, lane, t, g, env_ids, ctr_arr);
 }
 
 // Leaf expansion (MCTS.py:84-115) and backup (MCTS.py:154-164) of this simulation, then -
 // when do_select - the next simulation's descent for the same game (one kernel boundary per
 // simulation fewer).  One wave per game.
-__device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane);
+__device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane, int t, int g);
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
     EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr) {
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
     if (d.done[e]) return;
-    expand_backup_game(d, e, lane);
+    // the game's tree and generation, once for the expansion, the backup and the descent
+    const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
+    const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
+    const bool idle = d.idle[e] != 0;  // (loaded with them, not after the backup)
+    expand_backup_game(d, e, lane, t, g);
     if (do_select) {
+        if (idle) {
+            select_none(d, e, lane);
+            return;
+        }
         wave_sync();  // this wave's backup writes (edges, slots, Ns) precede its descent's reads
-        select_game(d, e, lane, env_ids, ctr_arr);
+        select_game(d, e, lane, t, g, env_ids, ctr_arr);
     }
 }
 
-__device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane) {
-    const int t = tree_of(d, e);
-    const int g = d.gen[t];
+__device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane, int t, int g) {
     PyV res{d.res_v[e], d.res_t[e]};
     uint32_t end_id = 0;  // id + 1 of the node the path's last edge leads to, if any
     if (d.leaf_flag[e]) {

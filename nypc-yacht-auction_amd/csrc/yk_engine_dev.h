@@ -5,6 +5,7 @@
 // throughout: each unit compiles its own copy.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #include <type_traits>
 
@@ -169,6 +170,27 @@ __device__ __forceinline__ void st_state(yk_state_t* p, const YkS& s) {
         q[k] = make_uint4((uint32_t)s.w[2 * k], (uint32_t)(s.w[2 * k] >> 32), (uint32_t)s.w[2 * k + 1],
                           (uint32_t)(s.w[2 * k + 1] >> 32));
 }
+// A record's words after the key (bytes 64 .. 95), as one batch of two 16-byte loads: everything a
+// descent level reads of its node but the state.  Issued together (and with the key's four loads
+// where the level also needs the state), one round trip brings them all.
+struct NodeF {
+    uint64_t hash, vinfo;
+    uint32_t p_off, nvalid, Ns, first_j;
+};
+static_assert(offsetof(NodeRec, hash) == 64 && offsetof(NodeRec, p_off) == 80 && offsetof(NodeRec, first_j) == 92,
+              "ld_node reads NodeRec bytes 64 .. 95 as two uint4");
+__device__ __forceinline__ NodeF ld_node(const NodeRec* r) {
+    const uint4* q = reinterpret_cast<const uint4*>(r);
+    const uint4 a = q[4], b = q[5];
+    return NodeF{(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32), b.x, b.y, b.z, b.w};
+}
+// Every lane loaded the same record: as scalars, the tests on the fields compare scalars and a
+// level's addresses are scalar arithmetic (fewer vector registers hold pieces of the record)
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ uint64_t uni(uint64_t x) { return (uint64_t)uni((uint32_t)x) | ((uint64_t)uni((uint32_t)(x >> 32)) << 32); }
+__device__ __forceinline__ NodeF uniform(const NodeF& f) {
+    return NodeF{uni(f.hash), uni(f.vinfo), uni(f.p_off), uni(f.nvalid), uni(f.Ns), uni(f.first_j)};
+}
 __device__ __forceinline__ bool key_eq(const NodeRec& r, const YkS& s) {
     bool eq = true;
 #pragma unroll
@@ -208,8 +230,10 @@ __device__ __forceinline__ uint64_t index_hash(const YkS& s) {
     return ((uint64_t)b << 32) | a;
 }
 
-// open-addressing lookup; returns node id or -1.  Uniform across the wave.
-__device__ __forceinline__ int lookup(const EngDev& d, int g, int t, const YkS& s, uint64_t h) {  // t: tree
+// open-addressing lookup; returns node id or -1.  Uniform across the wave.  The probe reads the whole
+// record to compare hash and key, so `f` gets the matched record's other fields from that same
+// round trip (a descent level then needs no second one for them).
+__device__ __forceinline__ int lookup(const EngDev& d, int g, int t, const YkS& s, uint64_t h, NodeF& f) {  // t: tree
     const uint32_t* hx = d.hidx[g] + (long)t * d.HCAP;
     const NodeRec* nodes = d.nodes[g] + (long)t * d.NCAP;
     const uint32_t mask = (uint32_t)d.HCAP - 1;
@@ -218,10 +242,15 @@ __device__ __forceinline__ int lookup(const EngDev& d, int g, int t, const YkS& 
         const uint32_t v = hx[slot];
         if (v == 0) return -1;
         const NodeRec& r = nodes[v - 1];
-        if (r.hash == h && key_eq(r, s)) return (int)(v - 1);
+        f = ld_node(&r);
+        if ((f.hash == h) & key_eq(r, s)) return (int)(v - 1);  // ('&': one wait for the whole batch)
         slot = (slot + 1) & mask;
     }
     return -1;
+}
+__device__ __forceinline__ int lookup(const EngDev& d, int g, int t, const YkS& s, uint64_t h) {
+    NodeF f;
+    return lookup(d, g, t, s, h, f);
 }
 __device__ __forceinline__ bool insert_index(const EngDev& d, int g, int t, uint64_t h, uint32_t id) {
     uint32_t* hx = d.hidx[g] + (long)t * d.HCAP;

@@ -108,17 +108,17 @@ int yk_diag_select(uint64_t* out, int n) {  // HOST out[n][16]; resets the accum
 # + backup, 8-10 expand phases, 12 backup, 13 the root's incremental scan (root_scan), 14 its entries
 ENGINE = [
     (r"^// \(the node / edge records, EngDev, the error bits and the tree lookups: yk_engine_dev\.h\)\n", "after", ENGINE_GLOBALS),
-    (r"^    PyV res\{0\.0, T_INT\};\n    // the root's pick", "before_line2", "    SEL_T0(t_all);\n"),
-    (r"^        if \(rc\.x != 0 && rc1\.z != RV_OFF\) \{  // k_root_sort ran this move.*\n", "after", "            SEL_T0(t_rs);\n            const uint64_t sc0 = scanned;\n"),
+    (r"^    PyV res\{0\.0, T_INT\};\n    // this level's node when it is known", "before_line2", "    SEL_T0(t_all);\n"),
+    (r"^        if \(rid != 0 && uni\(rc1\.z\) != RV_OFF\) \{  // k_root_sort ran this move.*\n", "after", "            SEL_T0(t_rs);\n            const uint64_t sc0 = scanned;\n"),
     (r"^            pre = pre_bj != -1;\n", "after", "            SEL_ACC(13, t_rs);\n            SEL_ADD(14, scanned - sc0);\n"),
-    (r"^        if \(known >= 0\) \{  // the cached child.*\n", "before", "        SEL_T0(t_lv);\n"),
+    (r"^        if \(!have\) \{\n", "before", "        SEL_T0(t_lv);\n"),
     (r"^        if \(V == 0\) \{  // no valid action: MCTS.py:141-147.*\n", "before", "        SEL_ACC(0, t_lv);\n        SEL_T0(t_sc);\n"),
     (r"^        const int bj = bj_out;\n", "after", "        SEL_ACC(1, t_sc);\n        SEL_ADD(4, 1);\n        SEL_ADD(5, V);\n        SEL_T0(t_st);\n"),
     (r"^        s = canonical\(s, np\);  // MCTS.py:150\n", "after", "        SEL_ACC(2, t_st);\n"),
     (r"^        atomicAdd\(gs \+ 8, \(unsigned long long\)gathered\);\n    \}\n\}\n", "before_last_brace", "    SEL_ACC(3, t_all);\n"),
-    (r"^    if \(d\.done\[e\]\) return;\n    expand_backup_game\(d, e, lane\);\n", "replace",
-     "    if (d.done[e]) return;\n" + XSPAN_BEGIN + "    expand_backup_game(d, e, lane);\n" + XSPAN_MID),
-    (r"^        select_game\(d, e, lane, env_ids, ctr_arr\);\n    \}\n\}\n\n__device__ __forceinline__ void expand_backup_game",
+    (r"^    if \(d\.done\[e\]\) return;\n    // the game's tree and generation, once", "after_line1", XSPAN_BEGIN),
+    (r"^    expand_backup_game\(d, e, lane, t, g\);\n", "after", XSPAN_MID),
+    (r"^        select_game\(d, e, lane, t, g, env_ids, ctr_arr\);\n    \}\n\}\n\n__device__ __forceinline__ void expand_backup_game",
      "replace_fn", None),
     (r"^        // ---- prior, Ps \* valids \(MCTS.py:88\)", "before", "        SEL_T0(t_x0);\n"),
     (r"^        // numpy pairwise_sum on the leaf:", "before", "        SEL_ACC(8, t_x0);\n        SEL_T0(t_x1);\n"),
