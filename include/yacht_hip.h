@@ -347,7 +347,9 @@ int yk_engine_kernel_times(yk_engine_t* eng, double* ms, int64_t* launches);
 int yk_engine_stats(yk_engine_t* eng, int64_t* out);
 /* Further counters of the last batch, summed over games; writes out[0 .. n-1] of:
  * 0 edges gathered by the UCB scans (one 16-B edge per visited entry scanned, MCTS.py:122-133; with
- *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env) */
+ *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env)
+ * 1-3 expansions whose prior took the window, the sparse and the general path (their sum: stats 0;
+ *   YK_PRIOR_FAST=0 sends every one through the general path) */
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)
@@ -372,6 +374,11 @@ int yk_engine_predictions(yk_engine_t* eng, float* pi, float* v, yk_state_t* lea
  * noise found it and P' as it left it, 0 at invalid actions and for moves >= the game's n_moves.
  * YK_ERR_STATE unless the engine has both record_predictions and noise on and has played a batch. */
 int yk_engine_root_priors(yk_engine_t* eng, float* before, float* after);
+/* test: HOST p[3226] = the prior P stored in the tree for the root of game `game`'s current move (tree
+ * `game`), dense by action, 0 at invalid actions: what the expansion wrote (MCTS.py:90-107) and the UCB scans
+ * read.  YK_ERR_STATE while no descent of the move has found the root in the tree (before the move's second
+ * simulation on a fresh tree). */
+int yk_engine_root_prior(yk_engine_t* eng, int game, float* p);
 /* The noise itself: eta[i*3226 + j], j < nvalid[i], is the Dirichlet(alpha) sample over nvalid[i] valid
  * actions that game env_ids[i] gets at move moves[i] under `seed` (0 for j >= nvalid[i]; nvalid is clamped
  * to 0..3226) - the same device function as the engine's, so the same bits.  Defined by Philox4x32-10 with

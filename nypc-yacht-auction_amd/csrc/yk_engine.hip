@@ -97,6 +97,17 @@ constexpr int pw_tmax() {
 }
 constexpr int PW_GMAX = pw_gmax();  // 8-element groups in the longest leaf
 constexpr int PW_TMAX = pw_tmax() > 0 ? pw_tmax() : 1;  // longest n % 8 tail
+constexpr int pw_lmax() {
+    const PwPlan p = make_plan();
+    int l = 0;
+    for (int i = 0; i < p.nleaf; i++) l = p.len[i] > l ? p.len[i] : l;
+    return l;
+}
+// A 5-dice leaf's valid actions are NCOMB apart (one per unused category): no two share a leaf of the
+// plan, so a leaf's partial sum is then that one prior (the expansion's sparse path)
+static_assert(NCOMB > pw_lmax(), "two category starts could share a leaf of the pairwise plan");
+static_assert(PF_WCAP % 8 == 0 && PF_WCAP >= 16 && GAMES_PER_BLOCK * PF_WCAP * 4 <= 40 * 1024,
+              "the prior window: whole float4 pairs, a slot per category, 16 waves per CU");
 
 // getValidMoves of player 1 as wave-uniform scalars (the same test as action_valid)
 struct ValidQ {
@@ -700,10 +711,34 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
         const bool rec = d.rec_pred && (e % d.rec_stride) == 0 && pidx < d.max_exp;
         const long rslot = rec ? (long)(e / d.rec_stride) * d.max_exp + pidx : 0;
         bool masked = false;  // q / qt already hold Ps * valids
+        // The compact-first prior of a leaf with a small valid set: each unnormalised
+        // prior is computed once, in compact order, and staged in the wave's LDS window; the pairwise
+        // sum's operands and the P write below read it back, so neither runs a validity test or an exp.
+        //   window (1): the valid actions span at most PF_WCAP floats (every bid node, a score node
+        //               whose unused categories lie close together); the window is laid out by action
+        //               from wbase, zeros between the categories
+        //   sparse (2): a 5-dice score node, one action per unused category; slot = the category
+        // A scalar choice per wave.  The general path (0) is the dense pass over all 3226 actions.
+        __shared__ __attribute__((aligned(16))) float s_win[GAMES_PER_BLOCK][PF_WCAP];
+        float* win = s_win[threadIdx.x >> 6];  // (only this wave touches it: wave_sync orders it)
+        int fast = 0, wbase = 0, wlen = 0;
+        if (d.prior_fast && V > 0) {
+            if (valid.mode == 0 && valid.n == 5) {
+                fast = 2;
+                wlen = 16;
+            } else {
+                const int a0 = __builtin_amdgcn_readfirstlane(compact_to_action(vi, 0));
+                const int a1 = __builtin_amdgcn_readfirstlane(compact_to_action(vi, V - 1));
+                wbase = a0 & ~7;  // (a float4 of the sum's layout lies wholly inside or outside)
+                wlen = (a1 + 1 - wbase + 7) & ~7;
+                fast = wlen <= PF_WCAP ? 1 : 0;
+            }
+        }
+        // an action's slot in the window
+        const auto wslot = [&](int a) { return fast == 2 ? (a - NBID) / NCOMB : a - wbase; };
         if (d.prior == 0) {
             // pi = exp(log_softmax(logits)) (NNet.py:193) at the valid actions only: the forward
             // supplies each row's (max, log sum exp), so the invalid logits are never read
-            const float* x = d.logits + (long)e * PI_LD + st;
             const float2 ml = d.mlse[e];
             mx = ml.x;
             lse = ml.y;
@@ -719,6 +754,70 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                 }
                 lse = logf(ms);
             }
+            v = d.vpred[e];
+        } else {
+            v = hash_prior_v(hsh);
+        }
+        if (fast) {
+            for (int i = 4 * lane; i < wlen; i += 256) *reinterpret_cast<float4*>(win + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+            wave_sync();
+            const float* __restrict__ xr = d.logits + (long)e * PI_LD;
+            for (int j0 = lane; j0 < V; j0 += 256) {  // four gathers in flight per lane
+                float xa[4];
+                int aa[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int j = j0 + 64 * u;
+                    aa[u] = j < V ? compact_to_action(vi, j) : 0;
+                    xa[u] = (d.prior == 0 && j < V) ? xr[aa[u]] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (j0 + 64 * u < V)
+                        win[wslot(aa[u])] = d.prior == 0 ? softmax_p(xa[u], mx, lse) : hash_prior_pi(hsh, aa[u]);
+            }
+            wave_sync();
+            // the sum's operands from the window: zeros outside it
+            int soff = -8;               // sparse: where the leaf's one category start lies in it (none: -8)
+            float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (fast == 2) {
+                const int c = st <= NBID ? 0 : (st - NBID + NCOMB - 1) / NCOMB;
+                const int o = NBID + NCOMB * c - st;
+                if (c < NCAT && o < nl) {
+                    const float pc = win[c];
+                    soff = o;
+                    sv = make_float4((o & 3) == 0 ? pc : 0.f, (o & 3) == 1 ? pc : 0.f, (o & 3) == 2 ? pc : 0.f,
+                                     (o & 3) == 3 ? pc : 0.f);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < PW_GMAX; j++) {
+                const int o = 8 * j + 4 * h;
+                float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (fast == 1) {
+                    const int i = st + o - wbase;
+                    if (j < G && (unsigned)i < (unsigned)wlen) w = *reinterpret_cast<const float4*>(win + i);
+                } else if (j < G && o == (soff & ~3)) {
+                    w = sv;
+                }
+                q[j] = w;
+            }
+#pragma unroll
+            for (int r = 0; r < PW_TMAX; r++) {
+                const int o = 8 * G + r, i = st + o - wbase;
+                float w = 0.f;
+                if (h == 0 && r < R) {
+                    if (fast == 1) {
+                        if ((unsigned)i < (unsigned)wlen) w = win[i];
+                    } else if (o == soff) {
+                        w = win[wslot(st + o)];
+                    }
+                }
+                qt[r] = w;
+            }
+            masked = true;
+        } else if (d.prior == 0) {
+            const float* x = d.logits + (long)e * PI_LD + st;
             // score actions at 10 dice (most leaves): a group a .. a + 3 (a = 0 mod 4) holds at
             // most two categories, a's and a + 2's (category starts are 202 + 252 c = 2 mod 4)
             static_assert(NBID % 4 == 2 && NCOMB % 4 == 0, "category starts are 2 mod 4");
@@ -747,7 +846,6 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
 #pragma unroll
             for (int r = 0; r < PW_TMAX; r++)
                 qt[r] = (h == 0 && r < R && valid(st + 8 * G + r)) ? softmax_p(x[8 * G + r], mx, lse) : 0.f;
-            v = d.vpred[e];
             masked = true;
         } else {
 #pragma unroll
@@ -759,7 +857,6 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             }
 #pragma unroll
             for (int r = 0; r < PW_TMAX; r++) qt[r] = (h == 0 && r < R) ? hash_prior_pi(hsh, st + 8 * G + r) : 0.f;
-            v = hash_prior_v(hsh);
         }
         // mask with the valid moves
 #pragma unroll
@@ -836,8 +933,9 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             uint16_t* S = d.arenaS + (long)t * d.AE + off;
             const float inv_fallback = V > 0 ? 1.0f / (float)V : 0.0f;
             // P over the compact valid set (ascending action): Ps / sum, or the uniform fallback
-            // (MCTS.py:90-107).  Written in compact order (coalesced), recomputing each prior
-            // exactly as above from the L2-resident logits row (or the hash).
+            // (MCTS.py:90-107).  Written in compact order (coalesced): each prior read back from the
+            // window, or on the general path recomputed exactly as above from the L2-resident logits
+            // row (or the hash).
             const float* __restrict__ xr = d.logits + (long)e * PI_LD;
             // the node summary: the pick of the node's first UCB scan (Ns = 0: every term is
             // u = (c p) sqe0, the scan's own operations and order), from the final p's
@@ -851,7 +949,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                 for (int u = 0; u < 4; u++) {
                     const int j = j0 + 64 * u;
                     aa[u] = j < V ? compact_to_action(vi, j) : 0;
-                    xa[u] = (d.prior == 0 && j < V) ? xr[aa[u]] : 0.f;
+                    xa[u] = (d.prior == 0 && !fast && j < V) ? xr[aa[u]] : 0.f;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
@@ -859,7 +957,9 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                     if (j < VP) {
                         float p = 0.0f;
                         if (j < V) {
-                            const float pa = d.prior == 0 ? softmax_p(xa[u], mx, lse) : hash_prior_pi(hsh, aa[u]);
+                            const float pa = fast            ? win[wslot(aa[u])]
+                                             : d.prior == 0 ? softmax_p(xa[u], mx, lse)
+                                                            : hash_prior_pi(hsh, aa[u]);
                             p = sum > 0.0f ? pa / sum : inv_fallback;
                             const float u0 = (d.c32 * p) * sqe0;
                             if (u0 > fb) {  // ascending j within the lane: strict '>' keeps the lowest
@@ -893,6 +993,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                 unsigned long long* gs = reinterpret_cast<unsigned long long*>(d.gstats + (long)e * GST);
                 atomicAdd(gs + 0, 1ull);
                 atomicAdd(gs + 3, (unsigned long long)V);
+                atomicAdd(gs + (fast == 1 ? 9 : fast == 2 ? 10 : 11), 1ull);  // the prior's path
                 atomicMax(gs + 4, (unsigned long long)(nid + 1));
                 atomicMax(gs + 6, (unsigned long long)(off + (uint32_t)VP));
             }
@@ -1679,6 +1780,10 @@ constexpr int YK_FPARTS_MAX = 4;
         // the same trees; the records' first_j is written either way)
         const char* en = getenv("YK_NODE_SUMMARY");
         d.node_summary = (en && en[0] == '0') ? 0 : 1;
+        // YK_PRIOR_FAST=0: every leaf's prior takes the dense pass (A/B, and the test that both give
+        // the same trees)
+        const char* ep = getenv("YK_PRIOR_FAST");
+        d.prior_fast = (ep && ep[0] == '0') ? 0 : 1;
         // YK_SPLIT_DESCENT=1 (measurement): k_expand_backup stops after the backup and each next
         // descent is its own k_select launch, so rocprofv3 times and counts the expansion + backup
         // and the descent apart (the same work: the trees are identical)
@@ -1931,9 +2036,12 @@ int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n) {
     std::vector<uint64_t> gs((size_t)d.E * GST);
     YK_HIP(hipDeviceSynchronize());
     YK_HIP(hipMemcpy(gs.data(), d.gstats, sizeof(uint64_t) * gs.size(), hipMemcpyDeviceToHost));
-    int64_t c[1] = {0};
-    for (int e = 0; e < d.E; e++) c[0] += (int64_t)gs[(size_t)e * GST + 8];
-    for (int i = 0; i < n; i++) out[i] = i < 1 ? c[i] : 0;
+    int64_t c[4] = {0, 0, 0, 0};  // scan edges; expansions by prior path: window, sparse, general
+    for (int e = 0; e < d.E; e++) {
+        c[0] += (int64_t)gs[(size_t)e * GST + 8];
+        for (int k = 0; k < 3; k++) c[1 + k] += (int64_t)gs[(size_t)e * GST + 9 + k];
+    }
+    for (int i = 0; i < n; i++) out[i] = i < 4 ? c[i] : 0;
     return YK_OK;
 }
 
@@ -2006,6 +2114,28 @@ int yk_engine_root_priors(yk_engine_t* eng, float* before, float* after) {
     YK_HIP(hipDeviceSynchronize());
     if (before) YK_HIP(hipMemcpy(before, eng->nz.prior_before, sizeof(float) * n, hipMemcpyDeviceToHost));
     if (after) YK_HIP(hipMemcpy(after, eng->nz.prior_after, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return YK_OK;
+}
+
+int yk_engine_root_prior(yk_engine_t* eng, int game, float* p) {
+    if (!eng || !p || game < 0 || game >= eng->d.E) return YK_ERR_ARG;
+    EngDev& d = eng->d;
+    uint4 rc[2];
+    YK_HIP(hipDeviceSynchronize());
+    YK_HIP(hipMemcpy(rc, d.root_c + 2 * game, sizeof(rc), hipMemcpyDeviceToHost));
+    if (rc[0].x == 0) return YK_ERR_STATE;  // no descent of the move found the root in the tree
+    const uint64_t x = (uint64_t)rc[1].x | ((uint64_t)rc[1].y << 32);  // (pack_vinfo)
+    VInfo vi;
+    vi.cats = x & 0xFFFFFFFFFFFFull;
+    vi.k = (int)((x >> 48) & 0xF);
+    vi.n = (int)((x >> 52) & 0xF);
+    vi.W = (int)(x >> 56);
+    vi.V = (int)rc[0].z;
+    std::vector<float> P((size_t)vi.V);
+    if (vi.V > 0)
+        YK_HIP(hipMemcpy(P.data(), d.arenaP + (size_t)game * d.AE + rc[0].y, sizeof(float) * P.size(), hipMemcpyDeviceToHost));
+    for (int a = 0; a < ASIZE; a++) p[a] = 0.f;
+    for (int j = 0; j < vi.V; j++) p[compact_to_action(vi, j)] = P[j];
     return YK_OK;
 }
 

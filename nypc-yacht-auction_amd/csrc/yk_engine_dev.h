@@ -28,6 +28,11 @@ constexpr int RO_K = 512;         // entries of the order kept: the top RO_K by 
                                   // about (visited edges + 1) of them, and past them falls back to a full scan
 constexpr int RV_CAP = 1024;      // visited root edges kept; more -> the move falls back to full scans
 constexpr uint32_t RV_OFF = 0xFFFFFFFFu;
+// The expansion's compact-first prior: floats of the per-wave LDS window, laid out by
+// action, that holds the unnormalised priors of a leaf whose valid actions span at most this many
+// (eight adjacent categories: 2024 with the alignment).  32 KB per block of 4 waves, so the 16 waves per
+// CU the expand kernel is budgeted for still fit the CU's 160 KB; 512 measured 0.28 % slower
+constexpr int PF_WCAP = 2048;
 
 // python value kinds on the search path (MCTS.py:82, 115, 147)
 enum : uint32_t { T_INT = 0, T_F64 = 1, T_F32 = 2 };
@@ -84,6 +89,8 @@ struct EngDev {
                            //        rv (RV_OFF: no P order this move), walk start: the order's entries
                            //        before it are all visited}; one 32-byte read for root_scan
     int node_summary;      // 1: a node's first UCB scan takes the record's first_j (YK_NODE_SUMMARY=0: full scans)
+    int prior_fast;        // 1: a leaf with a small valid set computes its priors in compact order (YK_PRIOR_FAST=0:
+                           //    every leaf takes the dense pass)
     int ro_k;              // entries of the root's order k_root_sort keeps (RO_K; YK_ROOT_K for the tests)
     uint32_t* rv;          // [T][RV_CAP] j | slot << 12 of each visited root edge
     uint16_t* ro_j;        // [T][RO_K] the root's top compact indices by descending P (ascending j on ties)
@@ -128,7 +135,7 @@ struct EngDev {
     yk_state_t* rec_leaf;  // [R][max_exp] the expanded leaf (canonical state)
     // stats
     uint64_t* gstats;      // [E][GST]: expansions, scanned, path edges, vnew, max nodes, max edges, max arena, sims,
-                           // edge gathers of the UCB scans
+                           // edge gathers of the UCB scans, expansions by prior path (window, sparse, general)
     uint32_t* err;         // [1] error bits
 };
 

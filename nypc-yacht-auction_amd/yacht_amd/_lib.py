@@ -108,6 +108,7 @@ SIGNATURES = {
     "yk_engine_records": [P, P, P, P, P, P, P, P, P, P],
     "yk_engine_predictions": [P, P, P, P, P],
     "yk_engine_root_priors": [P, P, P],
+    "yk_engine_root_prior": [P, I, P],
     "yk_dirichlet_noise": [U64, P, P, P, C.c_double, P, I, P],
     "yk_engine_record_bytes": [P],
     "yk_engine_pack_records": [P, P, C.c_int64, P],
@@ -136,7 +137,8 @@ _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_re
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
-          "yk_sample_draw", "yk_reanalyse_select", "yk_policies_from_counts", "yk_policies_splice"}
+          "yk_sample_draw", "yk_reanalyse_select", "yk_policies_from_counts", "yk_policies_splice",
+          "yk_engine_root_prior"}
 _lib = None
 
 

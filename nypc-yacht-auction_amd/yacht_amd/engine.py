@@ -113,7 +113,8 @@ class SelfPlayEngine:
     STAT_NAMES = ("expansions", "scanned", "moves", "errors", "max_nodes", "max_edges", "max_arena", "vnew",
                   "path_edges", "sims", "node_cap", "edge_cap", "arena_cap", "visit_cap", "groups",
                   "forward_parts")
-    COUNTER_NAMES = ("scan_edges",)  # yk_engine_counters
+    # yk_engine_counters: the scans' edge gathers; expansions by the prior's path
+    COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general")
 
     def stats(self) -> dict:
         out = np.zeros(16, dtype=np.int64)
