@@ -50,7 +50,8 @@ typedef struct { uint64_t w[8]; } yk_state_t;
 #define YK_ERR_STATE (-5)    /* engine misuse (e.g. MCTS root round went backwards) */
 #define YK_ERR_RANGE (-6)    /* a value outside the range an operation accepts: a net weight outside the fp16
                                 split's (|w| >= 65520: its hi plane overflows); a sampling weight that is negative
-                                or NaN, or weights whose total is not finite and > 0 (yk_sample_cdf) */
+                                or NaN, or weights whose total is not finite and > 0 (yk_sample_cdf); row indices not
+                                strictly ascending within a CSR (yk_policies_splice) or outside it (yk_policies_take) */
 
 /* per-element status of yk_step: the reference's exceptions */
 #define YK_ST_OK 0
@@ -222,7 +223,8 @@ int yk_sample_weights(const double* rows, int64_t ld, const int64_t* seg_ptr, co
 int yk_sample_cdf(const double* w, int64_t n, double* cdf, double* total, void* stream);
 /* m draws located in DEVICE cdf[n] (nondecreasing, as yk_sample_cdf leaves it) into DEVICE idx[m]: draw
  * j = first + r, r = 0 .. m-1, is Philox4x32-10 with counter (j lo, j hi, key, 0x20000000) - counter word 3 is 0
- * for the game streams, 0x40000000 for the symmetries and 0x80000000 | move for the root noise - under key
+ * for the game streams, 0x10000000 for the reanalysis, 0x30000000 for the playout schedule, 0x40000000 for the
+ * symmetries and 0x80000000 | move for the root noise - under key
  * (seed lo, seed hi); x = x0 | x1 << 32, u = (x >> 11) * 2^-53 (the game streams' uniform); t = u * cdf[n - 1];
  * idx[r] = #{i : cdf[i] <= t} (numpy's searchsorted(cdf, t, 'right')), and where that is n (u * total can round
  * up to the total) the first i with cdf[i] >= cdf[n - 1].  An element whose weight is zero, or absorbed by
@@ -243,8 +245,8 @@ int yk_sample_draw(const double* cdf, int64_t n, uint64_t seed, uint32_t key, ui
  *
  * Which rows.  Row i of the call is example k = index_base + i (a global index into the window's examples,
  * mod 2^64).  Its draw is Philox4x32-10 with counter (k lo, k hi, key, 0x10000000) - counter word 3 is 0 for the
- * game streams, 0x20000000 for the sampling, 0x40000000 for the symmetries and 0x80000000 | move for the root
- * noise - under key (seed lo, seed hi); x = x0 | x1 << 32, u = (x >> 11) * 2^-53 (the game streams' uniform).
+ * game streams, 0x20000000 for the sampling, 0x30000000 for the playout schedule, 0x40000000 for the symmetries
+ * and 0x80000000 | move for the root noise - under key (seed lo, seed hi); x = x0 | x1 << 32, u = (x >> 11) * 2^-53 (the game streams' uniform).
  * Row i is chosen iff u < fraction: 0 chooses none, 1 all.  DEVICE idx[0 .. m-1] = the chosen i ascending
  * (at most `capacity` are written; idx == NULL: count only), HOST *m = their number.  YK_ERR_CAPACITY when idx is
  * given and m > capacity.  NULL m, n < 0 or > 2^31 - 1, a fraction outside [0, 1] or NaN, capacity < 0 with
@@ -328,6 +330,27 @@ int yk_engine_destroy(yk_engine_t* eng);
  * Synchronises `stream` once per real move to test termination.  Returns YK_OK, or
  * YK_ERR_CAPACITY / YK_ERR_STATE if a device-side check failed (see yk_engine_stats). */
 int yk_selfplay(yk_engine_t* eng, uint64_t seed, uint32_t env_base, void* stream);
+/* Playout cap randomization (KataGo), a departure from the reference, opt-in; DESIGN.md section 6e.  Off
+ * (fast_sims = 0, the state of a new engine): every real move of yk_selfplay runs `sims` simulations.  On
+ * (fast_sims > 0): move m (0-based) of a yk_selfplay batch started with (seed, env_base) is a FULL move iff
+ * u < full_prob, u = ((x0 | x1 << 32) >> 11) * 2^-53 of Philox4x32-10 under key (seed lo, seed hi) with counter
+ * (m, env_base, 0, 0x30000000) - one draw per (batch, move), made on the host: all games of a batch are at the
+ * same move, so the lock-step loop itself runs fewer simulations; no game stream is consumed.  Every other
+ * move is a FAST move: fast_sims simulations instead of `sims`, no Dirichlet noise (its rows of
+ * yk_engine_root_priors stay zero), and info[e][m][6] = status | YK_REC_FAST.  Everything else is as before -
+ * the persistent tree, the temperature rule, the draws of the real step, the root value of
+ * record_root_values (a fast move's is recorded: TD(lambda) targets of earlier full moves read it).  A
+ * simulation is yk_mcts_search's: a batch's moves are that entry point's searches with sims = the move's cap.
+ * yk_arena and yk_mcts_search are never capped.  The cap lives in the engine, not in yk_engine_config_t, whose
+ * layout stays as it is.  fast_sims < 0, or on and not 2 <= fast_sims <= sims (one simulation on a fresh root
+ * leaves every visit count zero, and a temp-1 move cannot be sampled from that) or full_prob outside [0, 1] or
+ * NaN: YK_ERR_ARG, the engine unchanged.  Touches no device memory. */
+#define YK_REC_FAST 0x100 /* info[..][6] of a fast move: the step status (YK_ST_*, 0..5) | this bit */
+int yk_engine_set_playout_cap(yk_engine_t* eng, int fast_sims, double full_prob);
+/* The schedule itself, the bits yk_selfplay uses: HOST full[m] = 1 when move m of a batch started with (seed,
+ * env_base) is a full move under full_prob, else 0, m = 0 .. n_moves-1.  NULL full, n_moves < 0, full_prob
+ * outside [0, 1] or NaN: YK_ERR_ARG.  Host only. */
+int yk_playout_schedule(uint64_t seed, uint32_t env_base, double full_prob, int n_moves, uint8_t* full /* HOST */);
 /* Per-kernel timing with HIP events on the engine's stream; resets the accumulators.
  * enable = 0 off, k > 0 on: the per-move launches are timed every time, the per-simulation
  * forward / expand pair in every k-th simulation of a move (1 = all; an event record between
@@ -349,12 +372,14 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  * 0 edges gathered by the UCB scans (one 16-B edge per visited entry scanned, MCTS.py:122-133; with
  *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env)
  * 1-3 expansions whose prior took the window, the sparse and the general path (their sum: stats 0;
- *   YK_PRIOR_FAST=0 sends every one through the general path) */
+ *   YK_PRIOR_FAST=0 sends every one through the general path)
+ * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena) */
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)
- *   info[n][max_moves][8]    temp, player, action, expansions-so-far, root Ns, n visited, status, 0 (the
- *                            move's root value word with record_root_values, see yk_engine_config_t)
+ *   info[n][max_moves][8]    temp, player, action, expansions-so-far, root Ns, n visited, status (| YK_REC_FAST
+ *                            for a fast move of the playout cap), 0 (the move's root value word with
+ *                            record_root_values, see yk_engine_config_t)
  *   ctr[n][max_moves][2]     stream counter before the search / before the real step
  *   values[n][max_moves]     example value r*(-1)**(player != curPlayer) (Coach.py:72)
  *   final_states[n][8], n_moves[n]
@@ -445,12 +470,35 @@ int yk_examples_policies(const void* images, int n_images, int n_envs, int max_m
 int yk_examples_value_targets(const void* images, int n_images, int n_envs, int max_moves, int sims,
                               int64_t n_games, int64_t skip, int64_t n_examples, double beta, double lambda,
                               float* values, float* root_values, int64_t* n_missing, void* stream);
+/* The examples of full moves (playout cap).  Images, n_games and the example numbering
+ * are yk_examples_from_records' with skip = 0.  DEVICE idx[0 .. n_full-1] = the numbers, ascending, of the
+ * examples whose info[..][6] lacks YK_REC_FAST (at most `capacity` are written; idx == NULL: count only), HOST
+ * *n_full = their count.  Images of an engine without the cap give 0 .. total-1.  YK_ERR_CAPACITY when idx is
+ * given and n_full > capacity.  No atomics on data; the offsets come from the three-pass scan of the
+ * reanalysis, in which no workgroup waits for another; equal inputs give equal bits.  NULL images or n_full, a
+ * non-positive dimension, sims < 0, capacity < 0 with idx, more than 2^31 - 1 examples: YK_ERR_ARG (all but the
+ * last before anything touches the device).  Synchronises `stream`. */
+int yk_examples_full_rows(const void* images, int n_images, int n_envs, int max_moves, int sims, int64_t n_games,
+                          int32_t* idx, int64_t capacity, int64_t* n_full, void* stream);
+/* Rows of a CSR gathered.  The CSR (indptr[n + 1], cols, vals) and DEVICE idx[m], each within [0, n), in any
+ * order and with repeats -> the CSR (out_indptr[m + 1], out_cols, out_vals; out_indptr[0] = 0) and HOST *nnz:
+ * out row j is row idx[j], bit for bit.  Two phases as yk_policies_splice: out_cols == NULL writes out_indptr
+ * and *nnz only; else YK_ERR_CAPACITY if nnz > nnz_capacity.  An idx outside [0, n) is detected on the device:
+ * YK_ERR_RANGE, the outputs unspecified (nothing is written outside them).  m == 0: YK_OK, out_indptr[0] = 0,
+ * *nnz = 0.  No atomics on data, offsets from the same scan, equal inputs give equal bits.  An output that is
+ * one of the inputs, NULL indptr / out_indptr / nnz, NULL idx with m > 0, out_cols without out_vals / cols /
+ * vals or with nnz_capacity < 0, n or m < 0 or > 2^31 - 1: YK_ERR_ARG before anything touches the device.
+ * Synchronises `stream`. */
+int yk_policies_take(const int64_t* indptr, const int32_t* cols, const double* vals, int64_t n, const int32_t* idx,
+                     int64_t m, int64_t* out_indptr, int32_t* out_cols, double* out_vals, int64_t nnz_capacity,
+                     int64_t* nnz, void* stream);
 /* Symmetry augmentation of examples, a departure from the reference (whose getSymmetries is the identity),
  * opt-in: the game depends only on the multisets of the dice and is symmetric in the two auction groups,
  * while the features and the score actions are positional.  Row i of the call is example k = index_base + i
  * (a global index into the pooled examples); `flags` is a bit-set of YK_SYM_*; DESIGN.md section 7b-sym.
  *   Draws: draw d is Philox4x32-10 with counter (d, k & 0xffffffff, epoch_key, 0x40000000) - counter word 3
- *     is 0 for the game streams and 0x80000000 | move for the root noise - under key (seed lo, seed hi);
+ *     is 0 for the game streams, 0x10000000 / 0x20000000 / 0x30000000 for the reanalysis, the sampling and the
+ *     playout schedule, and 0x80000000 | move for the root noise - under key (seed lo, seed hi);
  *     below_d(m) = (x1 * m) >> 32 with x1 the output's word 1 (the game streams' rule).
  *   A list of length L with first draw b is permuted by perm = [0 .. L-1]; for m = L-1 .. 1:
  *     j = below_{b + (L-1-m)}(m + 1), swap perm[m], perm[j]; new[i] = old[perm[i]] (an old position p moves

@@ -1200,7 +1200,8 @@ __global__ __launch_bounds__(256) void k_root_sort(EngDev d) {
 }
 
 // getActionProb tail (MCTS.py:40-54) + Coach sampling/step (Coach.py:59-72).  One wave per game.
-__global__ __launch_bounds__(256) void k_move_end(EngDev d, int move) {
+// kind: 0, or YK_REC_FAST for a fast move of the playout cap (ORed into the record's status word).
+__global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind) {
     __shared__ uint32_t vis_all[GAMES_PER_BLOCK][ASIZE];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int e = d.e_lo + blockIdx.x * GAMES_PER_BLOCK + w;
@@ -1336,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move) {
     info[3] = (int32_t)d.gstats[(long)e * GST + 0];
     info[4] = (int32_t)root_ns;
     info[5] = nvis;
-    info[6] = st;
+    info[6] = st | kind;
     info[7] = 0;
     d.nmoves[e] = stepi;
     if (st != YK_ST_OK) {
@@ -1452,6 +1453,9 @@ struct yk_engine {
     bool noise = false;
     bool have_priors = false;    // the last batch was a self-play batch with noise: yk_engine_root_priors
     bool root_values = false;    // record_root_values: k_root_value after each k_move_end of yk_selfplay
+    int fast_sims = 0;           // playout cap (yk_engine_set_playout_cap; 0: off): a fast move's simulations
+    double full_prob = 1.0;      // and the probability that a move of a yk_selfplay batch is a full one
+    int64_t fast_moves = 0;      // lock-step moves of the last batch that ran with the fast cap
     yk_engine() = default;
     yk_engine(const yk_engine&) = delete;
     yk_engine& operator=(const yk_engine&) = delete;
@@ -1832,6 +1836,12 @@ int yk_engine_destroy(yk_engine_t* eng) {
 }  // extern "C"
 
 namespace {
+// Playout cap: whether move `move` of the batch (seed, env_base) is searched in full.  One
+// draw per (batch, move) in its own Philox domain, on the host: no game stream is consumed.
+bool playout_full(uint64_t seed, uint32_t env_base, int move, double full_prob) {
+    return u53(philox_u64(philox4x32_10(seed, (uint32_t)move, env_base, 0u, PHILOX_PLAYOUT))) < full_prob;
+}
+
 // One lock-step batch of complete games: self-play (Coach.executeEpisode) or, with
 // d.arena set, Arena.playGame against the uniform-random player.
 int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) {
@@ -1849,7 +1859,9 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
     YK_HIP(hipMemsetAsync(d.hidx[0], 0, sizeof(uint32_t) * (size_t)d.T * d.HCAP, s));
     const bool noise = eng->noise && !d.arena;  // the arenas never add noise
     const bool root_values = eng->root_values && !d.arena;  // nor do they record root values
+    const bool capped = eng->fast_sims > 0 && !d.arena;  // nor are they ever capped
     eng->have_priors = false;
+    eng->fast_moves = 0;
     if (root_values)  // info[..][7] = 0 also past a game's end: a zero word is "no value recorded"
         YK_HIP(hipMemsetAsync(d.rec_info, 0, sizeof(int32_t) * (size_t)d.E * d.M * 8, s));
     if (noise && eng->nz.prior_after) {  // dense by action: 0 off the valid set and past the game's end
@@ -1870,13 +1882,16 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
             hipLaunchKernelGGL(k_move_begin, game_grid(dg[g]), bb, 0, st[g], dg[g], move, 0);
             YK_LAUNCHED();
         }
+        // a fast move of the playout cap: fewer simulations, no root noise, the record's status word marked
+        const bool fast = capped && !playout_full(seed, env_base, move, eng->full_prob);
+        eng->fast_moves += fast;
         if (!d.arena || d.arena_agent == YK_PLAYER_MCTS || d.arena_opp == YK_PLAYER_MCTS) {
-            int rc = run_sims(eng, G, st, d.sims, d.env_id, d.ctr, noise ? move : -1);
+            int rc = run_sims(eng, G, st, fast ? eng->fast_sims : d.sims, d.env_id, d.ctr, noise && !fast ? move : -1);
             if (rc) return rc;
         }
         for (int g = 0; g < G; g++) {
             prof_mark(eng, g, KC_MOVE_END, st[g]);
-            hipLaunchKernelGGL(k_move_end, game_grid(dg[g]), bb, 0, st[g], dg[g], move);
+            hipLaunchKernelGGL(k_move_end, game_grid(dg[g]), bb, 0, st[g], dg[g], move, fast ? YK_REC_FAST : 0);
             YK_LAUNCHED();
             if (root_values) {  // the games with nmoves == move + 1; root[e] is still this move's root
                 prof_mark(eng, g, KC_ROOT_VALUE, st[g]);
@@ -1912,6 +1927,22 @@ int yk_selfplay(yk_engine_t* eng, uint64_t seed, uint32_t env_base, void* stream
     eng->d.arena = 0;
     eng->have_arena = false;
     return play_batch(eng, seed, env_base, as_stream(stream));
+}
+
+int yk_engine_set_playout_cap(yk_engine_t* eng, int fast_sims, double full_prob) {
+    if (!eng || fast_sims < 0) return YK_ERR_ARG;
+    // on: at least 2 simulations (one on a fresh root leaves every visit count zero), at most the full count
+    if (fast_sims > 0 && (fast_sims < 2 || fast_sims > eng->d.sims || !(full_prob >= 0.0 && full_prob <= 1.0)))
+        return YK_ERR_ARG;
+    eng->fast_sims = fast_sims;
+    eng->full_prob = full_prob;
+    return YK_OK;
+}
+
+int yk_playout_schedule(uint64_t seed, uint32_t env_base, double full_prob, int n_moves, uint8_t* full) {
+    if (!full || n_moves < 0 || !(full_prob >= 0.0 && full_prob <= 1.0)) return YK_ERR_ARG;
+    for (int m = 0; m < n_moves; m++) full[m] = playout_full(seed, env_base, m, full_prob) ? 1 : 0;
+    return YK_OK;
 }
 
 int yk_arena(yk_engine_t* eng, uint64_t seed, uint32_t env_base, const int32_t* agent_seat, int agent, int opponent,
@@ -2041,7 +2072,7 @@ int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n) {
         c[0] += (int64_t)gs[(size_t)e * GST + 8];
         for (int k = 0; k < 3; k++) c[1 + k] += (int64_t)gs[(size_t)e * GST + 9 + k];
     }
-    for (int i = 0; i < n; i++) out[i] = i < 4 ? c[i] : 0;
+    for (int i = 0; i < n; i++) out[i] = i < 4 ? c[i] : (i == 4 ? eng->fast_moves : 0);  // 4: playout-cap fast moves
     return YK_OK;
 }
 

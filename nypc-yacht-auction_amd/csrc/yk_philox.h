@@ -8,9 +8,10 @@
 //                                                   masks are such streams, env = 0x44524F50 + layer)
 //   PHILOX_REANALYSE  (k lo, k hi, key, .)          whether a refresh searches example k again
 //   PHILOX_SAMPLE     (j lo, j hi, key, .)          draw j of weighted minibatch sampling
+//   PHILOX_PLAYOUT    (move, env base, 0, .)        whether a self-play batch searches that move in full
 //   PHILOX_SYMMETRY   (draw, example, epoch key, .) the symmetry drawn for an example
 //   PHILOX_NOISE|move (draw, action, env, .)        Dirichlet root noise: every word with bit 31 set
-// A new feature takes the lowest multiple of 0x10000000 below 0x80000000 that is not listed (0x30000000
+// A new feature takes the lowest multiple of 0x10000000 below 0x80000000 that is not listed (0x50000000
 // next), names it here and in this comment, and uses no other word 3.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@ namespace yk {
 constexpr uint32_t PHILOX_GAME = 0u;
 constexpr uint32_t PHILOX_REANALYSE = 0x10000000u;
 constexpr uint32_t PHILOX_SAMPLE = 0x20000000u;
+constexpr uint32_t PHILOX_PLAYOUT = 0x30000000u;
 constexpr uint32_t PHILOX_SYMMETRY = 0x40000000u;
 constexpr uint32_t PHILOX_NOISE = 0x80000000u;
 

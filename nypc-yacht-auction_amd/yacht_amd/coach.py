@@ -15,6 +15,9 @@ any number of ranks (one process per GPU, torch.distributed):
 * reanalysis (opt-in, ``args.reanalyseFraction``; not in the reference): after the iteration's self-play, a
   Philox-chosen fraction of every older iteration's examples is searched again with the current net and
   their policy targets replaced (``replay.reanalyse``).  Every rank does all of it.
+* playout cap randomization (opt-in, ``args.playoutFastSims`` / ``playoutFullProb``; not in the reference;
+  DESIGN.md 6e): each move of a self-play batch is searched in full (numMCTSSims) with probability
+  playoutFullProb and with playoutFastSims simulations otherwise; only the full moves become examples.
 * held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
   iteration that never enter training, on which the previous and the new net are evaluated after
   train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
@@ -29,6 +32,7 @@ from __future__ import annotations
 import logging
 import os
 
+from ._lib import YK_REC_FAST
 from .engine import SelfPlayEngine
 from .mcts import MCTS
 from .state import ACTION_SIZE, unpack
@@ -40,12 +44,15 @@ GAME_MOVES = 48
 
 
 def examples_from_records(rec: dict, n_envs: int):
-    """Engine records -> per-game lists of (YachtState, pi list, v) as Coach.py:72 returns."""
+    """Engine records -> per-game lists of (YachtState, pi list, v) as Coach.py:72 returns.  A fast move of the
+    playout cap (info[6] & 0x100) is not an example."""
     out = []
     M = rec["states"].shape[1]
     for e in range(n_envs):
         ex = []
         for m in range(int(rec["n_moves"][e])):
+            if int(rec["info"][e, m, 6]) & YK_REC_FAST:
+                continue
             temp, _player, action = (int(x) for x in rec["info"][e, m, :3])
             a0, a1 = int(rec["visits_off"][e * M + m]), int(rec["visits_off"][e * M + m + 1])
             if temp == 0:
@@ -84,6 +91,12 @@ class Coach:
         from .replay import check_reanalyse_knobs
         self.reanalyse_fraction, self.reanalyse_sims = check_reanalyse_knobs(
             args.get("reanalyseFraction", 0.0), args.get("reanalyseSims", None), args.get("numMCTSSims", None))
+        # playout cap randomization: playoutFastSims simulations for the moves that are not drawn
+        # (playoutFullProb) to be searched in full; only the full moves become examples.  Unset: off
+        from .replay import check_playout_knobs
+        self.playout_fast_sims, self.playout_full_prob = check_playout_knobs(
+            args.get("playoutFastSims", None), args.get("playoutFullProb", None), args.get("numMCTSSims", None))
+        self.last_selfplay = None  # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims)
         self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
         self.holdout_eps = int(args.get("holdoutEps", 0) or 0)
@@ -116,7 +129,9 @@ class Coach:
                               dirichlet_alpha=self.args.get("dirichletAlpha", 0.0),
                               dirichlet_eps=self.args.get("dirichletEpsilon", 0.0),
                               # each move's root value in the records, only when the value targets use it
-                              record_root_values=self._value_targets_on())
+                              record_root_values=self._value_targets_on(),
+                              # the playout cap; the held-out games are played under the same config
+                              playout_fast_sims=self.playout_fast_sims, playout_full_prob=self.playout_full_prob)
 
     def _value_targets_on(self) -> bool:
         return (self.value_mix, self.value_lambda) != (0.0, 1.0)
@@ -145,11 +160,17 @@ class Coach:
         try:
             eng.run(self.game.rng.seed, base + lo)
             img = eng.pack_records()
+            sims_run = eng.stats()["sims"]
         finally:
             eng.close()
         gathered = D.allgather_records(img)
-        return examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen,
-                                    value_mix=self.value_mix, value_lambda=self.value_lambda)
+        shard = examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen,
+                                     value_mix=self.value_mix, value_lambda=self.value_lambda,
+                                     full_only=self.playout_fast_sims > 0)
+        self.last_selfplay = dict(searched=shard.n_searched, kept=len(shard), sims=sims_run)
+        log.info("SELF-PLAY %d moves searched, %d examples kept, %d lock-step sims run (this rank)"
+                 % (shard.n_searched, len(shard), sims_run))
+        return shard
 
     def reanalyseWindow(self, iteration: int):
         """The reanalysis of iteration `iteration`: every item of trainExamplesHistory but the

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import YkEngineConfigFull, call, lib, stream_ptr
+from ._lib import YK_REC_FAST, YkEngineConfigFull, call, lib, stream_ptr
 
 ACTION_SIZE = 3226
 
@@ -23,7 +23,8 @@ class SelfPlayEngine:
                  prior: str = "net", max_moves: int = 64, record_predictions: bool = False,
                  max_expansions: int = 0, arena_entries: int = 0, record_stride: int = 1, groups: int = 0,
                  dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
-                 dirichlet_eps: float = 0.0, record_root_values: bool = False):
+                 dirichlet_eps: float = 0.0, record_root_values: bool = False, playout_fast_sims: int = 0,
+                 playout_full_prob: float = 1.0):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -45,6 +46,15 @@ class SelfPlayEngine:
         call("yk_engine_create", C.byref(h), C.byref(self.cfg), C.c_void_p(net.handle if net is not None else None))
         self.handle = h.value
         self.n_envs, self.sims, self.max_moves = n_envs, sims, max_moves
+        # playout cap randomization in run() (never in arena()): each move of a batch is searched
+        # in full with probability playout_full_prob, else with playout_fast_sims simulations; 0 is off
+        self.playout_fast_sims, self.playout_full_prob = int(playout_fast_sims), float(playout_full_prob)
+        if self.playout_fast_sims != 0:
+            try:
+                call("yk_engine_set_playout_cap", self.handle, self.playout_fast_sims, self.playout_full_prob)
+            except Exception:
+                self.close()
+                raise
         self.opponent_net = opponent_net
         if opponent_net is not None:
             # MCTS vs MCTS with two nets, each seat its own tree (the gating arena, Coach.py:117-139)
@@ -114,7 +124,8 @@ class SelfPlayEngine:
                   "path_edges", "sims", "node_cap", "edge_cap", "arena_cap", "visit_cap", "groups",
                   "forward_parts")
     # yk_engine_counters: the scans' edge gathers; expansions by the prior's path
-    COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general")
+    # fast_moves: the lock-step moves of the last batch that ran with the fast playout cap
+    COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general", "fast_moves")
 
     def stats(self) -> dict:
         out = np.zeros(16, dtype=np.int64)
@@ -145,6 +156,8 @@ class SelfPlayEngine:
                    visits_off=voff.reshape(-1)[:E * M + 1], visits=visits[:int(nv[0])])
         if self.cfg.record_root_values:
             rec["root_values"] = decode_root_values(info[:, :, 7])  # float32 [n, max_moves], NaN where absent
+        if self.playout_fast_sims > 0:  # bool [n, max_moves]: the played moves searched with the fast cap
+            rec["fast"] = ((info[:, :, 6] & YK_REC_FAST) != 0) & (np.arange(M)[None, :] < nm[:, None])
         return rec
 
     def predictions(self, leaves: bool = False):
@@ -196,6 +209,15 @@ class SelfPlayEngine:
             self.close()
         except Exception:
             pass
+
+
+def playout_schedule(seed: int, env_base: int, full_prob: float, n_moves: int) -> np.ndarray:
+    """yk_playout_schedule: bool[n_moves], True where move m of a self-play batch started with (seed, env_base)
+    is searched in full under full_prob.  Host only."""
+    full = np.zeros(max(int(n_moves), 1), dtype=np.uint8)
+    call("yk_playout_schedule", seed & (2**64 - 1), env_base & (2**32 - 1), float(full_prob), int(n_moves),
+         full.ctypes.data)
+    return full[:int(n_moves)].astype(bool)
 
 
 def decode_root_values(words: np.ndarray) -> np.ndarray:

@@ -371,10 +371,59 @@ def policies_splice(policies, idx, new_policies):
     return out_ip, out_cols, out_vals
 
 
+# ---------------------------------------------------------------- playout cap
+def examples_full_rows(images, n_envs: int, max_moves: int, sims: int, n_games: int = -1, count_only: bool = False,
+                       stream=None):
+    """The examples of full moves in record images (yk_examples_full_rows): images a device uint8 tensor
+    [R, nbytes] as examples_from_images takes it, the examples numbered as yk_examples_from_records numbers
+    them with skip = 0.  Returns the numbers of the examples whose move was not a fast move of the playout
+    cap as a device int32 tensor, ascending - or only their count with count_only.  Synchronises."""
+    import ctypes as C
+    imgs = images.reshape(images.shape[0] if images.dim() > 1 else 1, -1).contiguous()
+    args = (ptr(imgs), int(imgs.shape[0]), int(n_envs), int(max_moves), int(sims), int(n_games))
+    sp = stream_ptr(stream)
+    m = C.c_int64()
+    call("yk_examples_full_rows", *args, None, 0, C.byref(m), sp)
+    if count_only:
+        return int(m.value)
+    idx = torch.empty(int(m.value), dtype=torch.int32, device="cuda")
+    if m.value:
+        call("yk_examples_full_rows", *args, ptr(idx), int(m.value), C.byref(m), sp)
+    return idx
+
+
+def policies_take(policies, idx):
+    """Rows idx of a policy CSR (yk_policies_take): idx a device int32 tensor within the CSR's rows, in any
+    order and with repeats; out row j is row idx[j] bit for bit.  Returns the device CSR (pi_indptr, pi_cols,
+    pi_vals); the input is not modified.  ValueError for an index out of range.  Synchronises."""
+    import ctypes as C
+    indptr, cols, vals = _csr(policies)
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise TypeError("idx must be an int32 vector")
+    n, m = int(indptr.numel()) - 1, int(idx.numel())
+    out_ip = torch.empty(m + 1, dtype=torch.int64, device="cuda")
+    nnz = C.c_int64()
+    # (an empty CSR's cols / vals may have no storage: any non-null pointer does, nothing reads it)
+    src = (ptr(indptr), ptr(cols) or ptr(indptr), ptr(vals) or ptr(indptr), n, ptr(idx) if m else None, m)
+    try:
+        call("yk_policies_take", *src, ptr(out_ip), None, None, 0, C.byref(nnz), stream_ptr())
+        k = int(nnz.value)
+        out_cols = torch.empty(k, dtype=torch.int32, device="cuda")
+        out_vals = torch.empty(k, dtype=torch.float64, device="cuda")
+        if k:
+            call("yk_policies_take", *src, ptr(out_ip), ptr(out_cols), ptr(out_vals), k, C.byref(nnz), stream_ptr())
+    except _lib.YkError as e:
+        if e.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError(f"idx must lie within 0 .. {n - 1}") from None
+    return out_ip, out_cols, out_vals
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
-           "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice", "_lib"]
+           "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice",
+           "examples_full_rows", "policies_take", "_lib"]
 
 
 def greedy_action(states):

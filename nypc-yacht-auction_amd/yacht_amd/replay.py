@@ -21,6 +21,7 @@ import torch
 from ._lib import YK_ERR_STATE, YK_OK, YkError, call, lib, stream_ptr
 from .kernels import augment_examples  # (a random symmetry of every example; listed with the buffer's functions)
 from .kernels import policies_from_counts, policies_splice, reanalyse_select  # (the reanalysis' device calls)
+from .kernels import examples_full_rows, policies_take  # (the playout cap's: the full moves' examples)
 
 
 def _vcap(max_moves: int, sims: int) -> int:
@@ -38,13 +39,17 @@ class ExampleShard:
     ``values`` is what NNetWrapper.train fits the value head to.  By default it is the outcome z; built
     with ``value_mix`` / ``value_lambda`` it is the search-value target, and the shard
     also carries ``outcomes`` (z, float32) and ``root_values`` (each move's root value, float32).  The
-    tuples, ``policies["values64"]`` and the examples files keep the reference's v, the outcome."""
+    tuples, ``policies["values64"]`` and the examples files keep the reference's v, the outcome.
+
+    ``n_searched`` (shards built from record images) is the number of moves the images hold for the shard's
+    games, before the playout cap's filter (``full_only``) and the ``maxlen`` cut."""
 
     def __init__(self, states, targets, values, policies=None, outcomes=None, root_values=None):
         self.states, self.targets, self.values = states, targets, values
         self.policies = policies
         self.outcomes = values if outcomes is None else outcomes
         self.root_values = root_values
+        self.n_searched = None
         self.reanalysis = None  # replay.reanalyse's report on the shard it returns: {"n", "n_empty", "chunks"}
         self._host = None
 
@@ -93,6 +98,35 @@ def check_value_knobs(value_mix, value_lambda):
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"value_lambda must lie in [0, 1], got {value_lambda!r}")
     return beta, lam
+
+
+def check_playout_knobs(playoutFastSims=None, playoutFullProb=None, numMCTSSims=None):
+    """(fast_sims, full_prob) of the playout cap randomization as (int, float): playoutFastSims
+    unset or 0 is off, else an int with 2 <= playoutFastSims <= numMCTSSims (one simulation on a fresh root
+    leaves every visit count zero); playoutFullProb (default 1) in (0, 1] with the cap on - at 0 no move would
+    be a training example.  ValueError otherwise, and for a playoutFullProb != 1 while the cap is off (it would
+    silently do nothing)."""
+    fast = 0 if playoutFastSims is None else playoutFastSims
+    if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or fast < 0:
+        raise ValueError(f"playoutFastSims must be an int >= 2 (or 0 / unset: off), got {playoutFastSims!r}")
+    p = float(1.0 if playoutFullProb is None else playoutFullProb)
+    if not 0.0 <= p <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"playoutFullProb must lie in [0, 1], got {playoutFullProb!r}")
+    fast = int(fast)
+    if fast == 0:
+        if p != 1.0:
+            raise ValueError("playoutFullProb needs playoutFastSims: without a fast cap every move is searched in "
+                             "full and the probability would do nothing")
+        return 0, 1.0
+    sims = numMCTSSims
+    if sims is None or isinstance(sims, bool) or int(sims) != sims:
+        raise ValueError(f"playoutFastSims needs numMCTSSims, got {numMCTSSims!r}")
+    if not 2 <= fast <= int(sims):
+        raise ValueError(f"playoutFastSims must lie in 2 .. numMCTSSims = {int(sims)}, got {playoutFastSims!r}")
+    if p <= 0.0:
+        raise ValueError("playoutFullProb must be > 0 with playoutFastSims set: no move would be searched in full, "
+                         "and there would be no training examples")
+    return fast, p
 
 
 def check_sample_knobs(trainSteps=0, sampleRecency=1.0, sampleSurprise=0.0):
@@ -151,7 +185,7 @@ def sample_segments(examples, gamma: float = 1.0):
 
 def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims: int, n_games: int = -1,
                          maxlen: int = None, stream=None, value_mix: float = 0.0,
-                         value_lambda: float = 1.0) -> ExampleShard:
+                         value_lambda: float = 1.0, full_only: bool = False) -> ExampleShard:
     """Record images (device uint8 [R, nbytes]: every rank's yk_engine_pack_records after the
     all-gather) -> ExampleShard of the first n_games games, keeping the last `maxlen` examples
     (the maxlenOfQueue deque, Coach.py:86-90).  The shard holds only compact arrays (examples and
@@ -160,8 +194,20 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
     value_mix (beta) and value_lambda (lambda), off at (0, 1): the shard's ``values`` become the
     search-value targets of yk_examples_value_targets - the outcome bootstrapped from the later moves' root
     values (lambda < 1) and mixed with the move's own (beta > 0); the images must then come from engines
-    created with record_root_values.  ``outcomes`` and the tuples keep z."""
+    created with record_root_values.  ``outcomes`` and the tuples keep z.
+
+    full_only (the playout cap): only the examples of full moves are kept.  Every array is first
+    built for all moves - the value targets must see whole games - then the rows yk_examples_full_rows names
+    are taken, and the last `maxlen` of those kept: maxlen counts training examples.  ``n_searched`` of the
+    shard is the number of moves before the filter."""
     beta, lam = check_value_knobs(value_mix, value_lambda)
+    if full_only:
+        every = examples_from_images(images, n_envs, max_moves, sims, n_games=n_games, maxlen=None, stream=stream,
+                                     value_mix=beta, value_lambda=lam)
+        idx = examples_full_rows(images, n_envs, max_moves, sims, n_games=n_games, stream=stream)
+        if maxlen is not None:
+            idx = idx[max(int(idx.numel()) - max(int(maxlen), 0), 0):].contiguous()
+        return _take_rows(every, idx)
     imgs = images.reshape(images.shape[0] if images.dim() > 1 else 1, -1).contiguous()
     R = imgs.shape[0]
     cnt = C.c_int64()
@@ -190,7 +236,9 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
          cols.data_ptr(), vals.data_ptr(), k, v64.data_ptr(), C.byref(nnz), sp)
     pol = dict(pi_indptr=indptr, pi_cols=cols[:k], pi_vals=vals[:k], values64=v64[:n])
     if (beta, lam) == (0.0, 1.0):
-        return ExampleShard(states[:n], targets[:n], values[:n], policies=pol)
+        shard = ExampleShard(states[:n], targets[:n], values[:n], policies=pol)
+        shard.n_searched = total
+        return shard
     tgt = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
     rootv = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
     missing = C.c_int64()
@@ -201,7 +249,25 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
                          "value_mix / value_lambda need engines created with record_root_values=True")
     if rc != YK_OK:
         raise YkError("yk_examples_value_targets", rc)
-    return ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n], root_values=rootv[:n])
+    shard = ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n], root_values=rootv[:n])
+    shard.n_searched = total
+    return shard
+
+
+def _take_rows(shard: ExampleShard, idx: torch.Tensor) -> ExampleShard:
+    """Rows idx (device int32, within the shard) of a shard with policies as a new shard: the fixed-width
+    columns by torch indexing, the policy CSR by yk_policies_take.  n_searched is carried over."""
+    rows = idx.to(torch.int64)
+    P = shard.policies
+    ip, cols, vals = policies_take((P["pi_indptr"], P["pi_cols"], P["pi_vals"]), idx)
+    pol = dict(pi_indptr=ip, pi_cols=cols, pi_vals=vals, values64=P["values64"].index_select(0, rows))
+    values = shard.values.index_select(0, rows)
+    same = shard.outcomes is shard.values
+    out = ExampleShard(shard.states.index_select(0, rows), shard.targets.index_select(0, rows), values, policies=pol,
+                       outcomes=None if same else shard.outcomes.index_select(0, rows),
+                       root_values=None if shard.root_values is None else shard.root_values.index_select(0, rows))
+    out.n_searched = shard.n_searched
+    return out
 
 
 # ---------------------------------------------------------------- reanalysis (DESIGN.md 7b-re)
@@ -259,6 +325,7 @@ def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: i
     def result(pol, targets, n_empty, chunks):
         out = ExampleShard(shard.states, targets, shard.values, policies=pol, outcomes=shard.outcomes,
                            root_values=shard.root_values)
+        out.n_searched = shard.n_searched
         out.reanalysis = dict(n=m, n_empty=n_empty, chunks=chunks)
         return out
     if m == 0:
@@ -426,5 +493,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_sample_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "augment_examples", "check_playout_knobs", "examples_full_rows", "policies_take", "check_sample_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
            "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]
