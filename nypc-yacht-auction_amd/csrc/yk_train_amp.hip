@@ -220,7 +220,7 @@ template <int KS, int NT, int RW, int DEF = 0>
 __device__ __forceinline__ void gemm_ring(const _Float16* A, int sa, float4 (&ring)[RW][NT], floatx4 (&acc)[NT],
                                           const float4* __restrict__ cur, const float4* __restrict__ nxt, int nt0) {
     static_assert(KS % RW == 0, "ring slots align with layers");
-    static_assert(0 <= DEF && DEF <= KS - RW + DEF && (DEF == 0 || RW == KS), "deferred refills within a one-matrix ring");
+    static_assert(0 <= DEF && DEF <= RW && DEF <= KS && (DEF == 0 || RW == KS), "deferred refills within a one-matrix ring");
     const int lane = threadIdx.x & 63;
     const _Float16* ap = A + (lane & 15) * sa + 8 * (lane >> 4);
 #pragma unroll

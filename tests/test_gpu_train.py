@@ -18,6 +18,8 @@ from oracle import spec
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from train_ref import _FixedDropout  # noqa: E402  (nn.Dropout with given keep masks)
+
 
 @pytest.fixture(scope="module")
 def T():
@@ -295,17 +297,6 @@ def test_dropout_rows_split_over_calls_equal_the_whole_batch(T, golden, amp, B):
     assert not np.allclose(g_wrong, half.grads().cpu().numpy())  # the offset selects other masks
 
 
-class _FixedDropout(torch.nn.Module):
-    """nn.Dropout with given keep masks: x * keep * 1/(1-p), as torch's dropout kernel scales."""
-
-    def __init__(self, p):
-        super().__init__()
-        self.scale, self.keep = 1.0 / (1.0 - p), None
-
-    def forward(self, x):
-        return x * (self.keep.to(x.dtype) * self.scale)
-
-
 def _torch_train_steps(sd0, H, NB, X, tg, vv, B, steps, amp, vw=1.5, masks=None, p=0.0):
     """The reference's train() inner loop (NNet.py:132-165) on the GPU: autocast('cuda') +
     GradScaler('cuda') (amp) or float32, AdamW(2e-3, 1e-4), clip 5.0; dropout 0, or - masks[k][L]
@@ -353,7 +344,7 @@ def _torch_train_steps(sd0, H, NB, X, tg, vv, B, steps, amp, vw=1.5, masks=None,
     return params, losses, grads1, (scaler.get_scale() if amp else None)
 
 
-@pytest.mark.parametrize("H,NB,B", [(256, 6, 512), (64, 1, 128)])
+@pytest.mark.parametrize("H,NB,B", [(256, 6, 512), (64, 1, 128), (128, 2, 128)])
 def test_amp_steps_vs_torch_autocast_gradscaler(T, golden, H, NB, B):
     """The mixed-precision mode against the reference's own GPU train step: torch autocast('cuda')
     + GradScaler('cuda') (NNet.py:141-155) on the same weights and minibatches, 3 steps.
