@@ -639,6 +639,49 @@ int yk_trainer_set_row_offset(yk_trainer_t* t, int64_t row0);
 /* HOST out[4] (amp mode): loss scale, growth tracker, optimiser steps taken, last step skipped */
 int yk_trainer_amp_state(yk_trainer_t* t, double* out);
 
+/* ---------------------------------------------------------------- averaged (EMA) weights (opt-in)
+ * A shadow e of the trainer's flat parameter buffer p that follows it, for play and gating; a departure from
+ * the reference, which plays the last minibatch's iterate.  Per element, in float32, each operation rounded
+ * once and never fused:  e <- e + w * (p - e).
+ *
+ * The weight of update t (t = updates made so far, 0-based), computed on the host in double:
+ *     d_t = min(decay, (1 + t) / (10 + t)),  w_t = (float)(1.0 - d_t)
+ * (the min is a warm-up: the first updates are not dominated by the initial shadow).  A pure host function,
+ * no device is touched.  decay outside [0, 1) or NaN, t < 0 or a NULL w: YK_ERR_ARG. */
+int yk_ema_weight(double decay, int64_t t, float* w /* HOST */);
+/* The kernel alone on caller-owned DEVICE buffers of n floats: ema[i] <- ema[i] + w * (params[i] - ema[i]).
+ * One grid-stride streaming pass on `stream` (no synchronisation); 16-byte accesses when both pointers are
+ * 16-byte aligned, scalar ones otherwise and for the tail - the pointers need float alignment only, and the
+ * bits do not depend on the path or the grid.  n == 0: YK_OK without a launch.  NULL pointers, n < 0, w outside
+ * [0, 1] or NaN: YK_ERR_ARG before anything touches the device. */
+int yk_ema_update(float* ema, const float* params, int64_t n, float w, void* stream);
+/* decay in (0, 1) with every >= 1 turns the average on: after every `every`-th yk_trainer_apply since the last
+ * update (yk_trainer_step* included), on that apply's stream and after its update launches, the shadow moves by
+ * w_t and the update is counted.  The first call that turns it on allocates the shadow (freed by
+ * yk_trainer_destroy); turning it on - the first time or after it was off - copies the current parameters into
+ * the shadow on the device and sets both counts to 0.  A call while it is on changes only the two knobs.
+ * decay == 0 (every >= 1) turns it off: the shadow is no longer used and yk_trainer_apply's launches are
+ * those of a trainer that never had one.  Anything else (NULL, decay < 0, >= 1 or NaN, every < 1): YK_ERR_ARG,
+ * the trainer as it was.  Synchronises the device when it copies.
+ *   A skipped AMP step counts: GradScaler's skip is decided on the device, the average counts every
+ * yk_trainer_apply, so t and w_t are host-known and no step reads the device; on a skipped step p is unchanged
+ * and the shadow moves once more toward the same p.
+ *   yk_trainer_set(which = 0) does not touch the shadow: it is a parameter load, and the caller decides with
+ * yk_trainer_ema_set. */
+int yk_trainer_set_ema(yk_trainer_t* t, double decay, int every);
+/* the shadow's DEVICE pointer (nparams floats, the layout of yk_trainer_buffers' params), for zero-copy views;
+ * YK_ERR_STATE when the average is off */
+int yk_trainer_ema_buffer(yk_trainer_t* t, float** ema);
+/* the shadow to HOST arrays in state_dict order, as yk_trainer_get takes them (NULL entries skipped);
+ * synchronises; YK_ERR_STATE when off */
+int yk_trainer_ema_get(yk_trainer_t* t, float* const* out);
+/* in: HOST arrays in state_dict order (NULL entries skipped) copied into the shadow, or in == NULL: the current
+ * parameters copied into it on the device.  updates >= 0 also sets the count of updates made (and the applies
+ * since the last one to 0); negative: both stay.  Synchronises; YK_ERR_STATE when off */
+int yk_trainer_ema_set(yk_trainer_t* t, const float* const* in, int64_t updates);
+/* HOST out[4]: decay, every, updates made, applies since the last update; all zeros when off */
+int yk_trainer_ema_state(yk_trainer_t* t, double* out /* HOST [4] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -562,6 +562,12 @@ struct yk_trainer {
     double host_loss[3] = {0, 0, 0};
     int64_t row_base = 0;        // global row of the next backward's first example (dropout)
     yk::AmpTrain* amp = nullptr;  // mixed-precision mode (yk_train_amp.hip)
+    // averaged weights (yk_trainer_set_ema; the kernel is yk_ema.hip's): E is allocated by the first call that
+    // turns the average on and stays in `mem`; ema_decay == 0 is off
+    float* E = nullptr;
+    double ema_decay = 0.0;
+    int ema_every = 1;
+    int64_t ema_updates = 0, ema_since = 0;  // updates made; applies since the last one
     yk_trainer() = default;
     yk_trainer(const yk_trainer&) = delete;
     yk_trainer& operator=(const yk_trainer&) = delete;
@@ -1023,13 +1029,26 @@ int yk_trainer_epoch_loss_end(yk_trainer_t* t, double* out) {
     return YK_OK;
 }
 
+// the averaged weights' part of an apply (on only): every ema_every-th apply moves the shadow toward P on `s`
+static int ema_apply(yk_trainer_t* t, hipStream_t s) {
+    if (++t->ema_since < t->ema_every) return YK_OK;
+    float w = 0.0f;
+    YK_TRY(yk_ema_weight(t->ema_decay, t->ema_updates, &w));
+    YK_TRY(yk_ema_update(t->E, t->P, t->nparams, w, s));
+    t->ema_updates += 1;
+    t->ema_since = 0;
+    return YK_OK;
+}
+
 int yk_trainer_apply(yk_trainer_t* t, void* stream) {
     if (!t) return YK_ERR_ARG;
     hipStream_t s = as_stream(stream);
     t->step += 1;  // (amp: the dropout stream's step; the optimiser's count of steps taken is on the device)
-    if (t->amp)
-        return yk::amp_apply(t->amp, t->acc + 2, t->cfg.max_grad_norm, t->cfg.lr, t->cfg.weight_decay, t->cfg.beta1,
-                             t->cfg.beta2, t->cfg.eps, t->cfg.dropout, t->cfg.seed, t->step, s);
+    if (t->amp) {
+        YK_TRY(yk::amp_apply(t->amp, t->acc + 2, t->cfg.max_grad_norm, t->cfg.lr, t->cfg.weight_decay, t->cfg.beta1,
+                             t->cfg.beta2, t->cfg.eps, t->cfg.dropout, t->cfg.seed, t->step, s));
+        return t->ema_decay > 0.0 ? ema_apply(t, s) : YK_OK;  // (a skipped step counts: the skip is the device's)
+    }
     const double b1 = t->cfg.beta1, b2 = t->cfg.beta2, st = (double)t->step;
     const double bc1 = 1.0 - std::pow(b1, st), bc2 = 1.0 - std::pow(b2, st);
     const float step_size = (float)(t->cfg.lr / bc1), bc2_sqrt = (float)std::sqrt(bc2);
@@ -1039,7 +1058,7 @@ int yk_trainer_apply(yk_trainer_t* t, void* stream) {
                        t->cfg.max_grad_norm, t->cfg.lr, t->cfg.weight_decay, t->cfg.beta1, t->cfg.beta2, t->cfg.eps,
                        step_size, bc2_sqrt);
     YK_LAUNCHED();
-    return YK_OK;
+    return t->ema_decay > 0.0 ? ema_apply(t, s) : YK_OK;
 }
 
 int yk_trainer_step(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const float* values,
@@ -1113,6 +1132,71 @@ int yk_trainer_set_row_offset(yk_trainer_t* t, int64_t row0) {
 int yk_trainer_amp_state(yk_trainer_t* t, double* out) {
     if (!t || !out || !t->amp) return YK_ERR_ARG;
     return yk::amp_state(t->amp, out);
+}
+
+// ---------------------------------------------------------------- averaged weights
+int yk_trainer_set_ema(yk_trainer_t* t, double decay, int every) {
+    if (!t || !(decay >= 0.0 && decay < 1.0) || every < 1) return YK_ERR_ARG;
+    if (decay == 0.0) {  // off: E stays allocated (it is the handle's), nothing reads it
+        t->ema_decay = 0.0;
+        t->ema_every = 1;
+        t->ema_updates = t->ema_since = 0;
+        return YK_OK;
+    }
+    if (t->ema_decay == 0.0) {  // off -> on: the shadow starts from the parameters as they are now
+        if (!t->E) YK_TRY(t->mem.alloc(&t->E, (size_t)t->nparams));
+        YK_HIP(hipDeviceSynchronize());
+        YK_HIP(hipMemcpy(t->E, t->P, sizeof(float) * t->nparams, hipMemcpyDeviceToDevice));
+        YK_HIP(hipDeviceSynchronize());
+        t->ema_updates = t->ema_since = 0;
+    }
+    t->ema_decay = decay;
+    t->ema_every = every;
+    return YK_OK;
+}
+
+int yk_trainer_ema_buffer(yk_trainer_t* t, float** ema) {
+    if (!t || !ema) return YK_ERR_ARG;
+    if (t->ema_decay == 0.0) return YK_ERR_STATE;
+    *ema = t->E;
+    return YK_OK;
+}
+
+int yk_trainer_ema_get(yk_trainer_t* t, float* const* out) {
+    if (!t || !out) return YK_ERR_ARG;
+    if (t->ema_decay == 0.0) return YK_ERR_STATE;
+    YK_HIP(hipDeviceSynchronize());
+    for (size_t k = 0; k < t->off.size(); k++)
+        if (out[k]) YK_HIP(hipMemcpy(out[k], t->E + t->off[k], sizeof(float) * t->len[k], hipMemcpyDeviceToHost));
+    return YK_OK;
+}
+
+int yk_trainer_ema_set(yk_trainer_t* t, const float* const* in, int64_t updates) {
+    if (!t) return YK_ERR_ARG;
+    if (t->ema_decay == 0.0) return YK_ERR_STATE;
+    YK_HIP(hipDeviceSynchronize());
+    if (!in) {
+        YK_HIP(hipMemcpy(t->E, t->P, sizeof(float) * t->nparams, hipMemcpyDeviceToDevice));
+    } else {
+        for (size_t k = 0; k < t->off.size(); k++)
+            if (in[k]) YK_HIP(hipMemcpy(t->E + t->off[k], in[k], sizeof(float) * t->len[k], hipMemcpyHostToDevice));
+    }
+    if (updates >= 0) {
+        t->ema_updates = updates;
+        t->ema_since = 0;
+    }
+    YK_HIP(hipDeviceSynchronize());
+    return YK_OK;
+}
+
+int yk_trainer_ema_state(yk_trainer_t* t, double* out) {
+    if (!t || !out) return YK_ERR_ARG;
+    const bool on = t->ema_decay > 0.0;
+    out[0] = on ? t->ema_decay : 0.0;
+    out[1] = on ? (double)t->ema_every : 0.0;
+    out[2] = on ? (double)t->ema_updates : 0.0;
+    out[3] = on ? (double)t->ema_since : 0.0;
+    return YK_OK;
 }
 
 }  // extern "C"

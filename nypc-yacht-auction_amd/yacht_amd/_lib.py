@@ -132,19 +132,27 @@ SIGNATURES = {
     "yk_playout_schedule": [U64, U32, C.c_double, I, P],
     "yk_examples_full_rows": [P, I, I, I, I, C.c_int64, P, C.c_int64, P, P],
     "yk_policies_take": [P, P, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, P],
+    "yk_ema_weight": [C.c_double, C.c_int64, P],
+    "yk_ema_update": [P, P, C.c_int64, C.c_float, P],
+    "yk_trainer_set_ema": [P, C.c_double, I],
+    "yk_trainer_ema_buffer": [P, P],
+    "yk_trainer_ema_get": [P, P],
+    "yk_trainer_ema_set": [P, P, C.c_int64],
+    "yk_trainer_ema_state": [P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
-# search-value targets, the held-out evaluation, the weighted sampling, the reanalysis and the playout cap (A/B
-# baselines may predate them)
+# search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap and the
+# averaged weights (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
           "yk_sample_draw", "yk_reanalyse_select", "yk_policies_from_counts", "yk_policies_splice",
           "yk_engine_root_prior", "yk_engine_set_playout_cap", "yk_playout_schedule", "yk_examples_full_rows",
-          "yk_policies_take"}
+          "yk_policies_take", "yk_ema_weight", "yk_ema_update", "yk_trainer_set_ema", "yk_trainer_ema_buffer",
+          "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state"}
 _lib = None
 
 

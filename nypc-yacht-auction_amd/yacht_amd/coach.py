@@ -96,6 +96,10 @@ class Coach:
         from .replay import check_playout_knobs
         self.playout_fast_sims, self.playout_full_prob = check_playout_knobs(
             args.get("playoutFastSims", None), args.get("playoutFullProb", None), args.get("numMCTSSims", None))
+        # averaged weights: NNetWrapper's knobs, checked here as well.  With emaDecay set the
+        # net that plays, gates and reanalyses is the averaged one (NNetWrapper.yk_net); learn's flow is unchanged
+        from .replay import check_ema_knobs
+        self.ema_decay, self.ema_every = check_ema_knobs(args.get("emaDecay", 0.0), args.get("emaEvery", 1))
         self.last_selfplay = None  # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims)
         self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
@@ -103,7 +107,8 @@ class Coach:
         if self.holdout_eps < 0:
             raise ValueError(f"holdoutEps must be >= 0, got {args.get('holdoutEps')!r}")
         self.holdoutHistory = []  # one ExampleShard per iteration, the trainExamplesHistory window
-        self.last_eval = None     # {"prev": ..., "new": ...} of the last iteration (NNetWrapper.evaluate's dicts)
+        self.last_eval = None     # {"prev": ..., "new": ...} of the last iteration (NNetWrapper.evaluate's dicts;
+        #                           with emaDecay also "new_raw": the new net's raw iterate)
         self.eval_history = []
         # the competitor network with the same args (Coach.py:26-27)
         self.pnet = nnet.__class__(game, args) if hasattr(nnet, "train") else None
@@ -254,10 +259,14 @@ class Coach:
                                   "new": self.nnet.evaluate(self.holdoutHistory)}
                 self.eval_history.append(self.last_eval)
                 pe, ne = self.last_eval["prev"], self.last_eval["new"]
+                raw = ""
+                if self.ema_decay > 0.0:  # what the average does: the same examples under the raw iterate
+                    self.last_eval["new_raw"] = self.nnet.evaluate(self.holdoutHistory, weights="raw")
+                    raw = " ; NEW raw loss %.4f" % self.last_eval["new_raw"]["loss"]
                 log.info("HELD-OUT %d examples, PREV / NEW : loss %.4f / %.4f ; policy_ce %.4f / %.4f ; top1 %.4f / "
-                         "%.4f ; value_mse %.4f / %.4f" % (ne["n"], pe["loss"], ne["loss"], pe["policy_ce"],
-                                                          ne["policy_ce"], pe["top1"], ne["top1"], pe["value_mse"],
-                                                          ne["value_mse"]))
+                         "%.4f ; value_mse %.4f / %.4f%s" % (ne["n"], pe["loss"], ne["loss"], pe["policy_ce"],
+                                                            ne["policy_ce"], pe["top1"], ne["top1"],
+                                                            pe["value_mse"], ne["value_mse"], raw))
                 t["eval"] = clock()
             log.info("PITTING AGAINST PREVIOUS VERSION")
             pwins, nwins, draws = GatingArena(self.game, self.pnet, self.nnet, a).playGames(

@@ -236,15 +236,46 @@ class NNetWrapper:
                               self.args.dropout)
         self._yk = None
         self._yk_version = None
+        # averaged weights (args.emaDecay > 0): self.nnet stays the raw iterate, the shadow is
+        # kept as a CPU state_dict (None: none yet - the raw weights are then the average of themselves)
+        self._ema_sd = None
+        self.ema_updates = 0
+        self._yk_raw = None
+        self._yk_raw_version = None
 
     def _weights_version(self):
         return tuple(p._version for p in self.nnet.parameters())
 
-    def yk_net(self) -> YkNet:
-        """Device weights for the kernels; rebuilt when the torch parameters change."""
+    def ema_knobs(self):
+        """(decay, every) of args.emaDecay / args.emaEvery (check_ema_knobs; decay 0: off)."""
+        from .replay import check_ema_knobs
+        return check_ema_knobs(self.args.get("emaDecay", 0.0), self.args.get("emaEvery", 1))
+
+    def ema_on(self) -> bool:
+        return self.ema_knobs()[0] > 0.0
+
+    def ema_state_dict(self):
+        """The weights that play: the shadow when there is one, else the raw weights."""
+        return self._ema_sd if self._ema_sd is not None else self.nnet.state_dict()
+
+    def _set_shadow(self, sd, updates):
+        self._ema_sd = None if sd is None else OrderedDict((k, sd[k].detach().to("cpu", torch.float32).clone())
+                                                          for k in self.nnet.state_dict().keys())
+        self.ema_updates = int(updates)
+        self._yk = None
+
+    def yk_net(self, raw=False) -> YkNet:
+        """Device weights for the kernels; rebuilt when the torch parameters change.  With averaged weights
+        (args.emaDecay) this is the averaged net - what predicts, plays, gates and reanalyses - and
+        raw=True the net of self.nnet, the optimiser's iterate (cached separately)."""
         v = self._weights_version()
+        if raw and self._ema_sd is not None:
+            if self._yk_raw is None or v != self._yk_raw_version:
+                self._yk_raw = YkNet(self.nnet.state_dict(), self.args.hidden, self.args.nblocks)
+                self._yk_raw_version = v
+            return self._yk_raw
         if self._yk is None or v != self._yk_version:
-            self._yk = YkNet(self.nnet.state_dict(), self.args.hidden, self.args.nblocks)
+            self._yk = YkNet(self.ema_state_dict(), self.args.hidden, self.args.nblocks)
             self._yk_version = v
         return self._yk
 
@@ -262,16 +293,19 @@ class NNetWrapper:
             raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
         return target
 
-    def evaluate(self, examples, target=None) -> dict:
+    def evaluate(self, examples, target=None, weights=None) -> dict:
         """Forward only, dropout off: YkNet.evaluate's numbers for this net on `examples` - every form
         train takes (tuples, an ExampleShard, a list of either).  The values are always the outcome
         (a shard's ``outcomes``, never its knob-dependent ``values``), so runs with different valueMix /
         valueLambda stay comparable.  Adds ``loss`` = policy term + vloss_weight * value_mse, the policy
         term being policy_ce, or policy_ce_soft when `target` (default args.policy_target) is "visits" -
         which needs the policies, as train does; with "argmax" the soft entries are None when the
-        examples carry no policies."""
+        examples carry no policies.  `weights`: "ema" (default; the weights that play - the averaged ones with
+        args.emaDecay, else the raw ones) or "raw" (self.nnet, the optimiser's iterate)."""
         from .replay import as_device_examples, as_device_policies
         target = self.eval_target(target)
+        if weights not in (None, "ema", "raw"):
+            raise ValueError(f"weights must be ema or raw, not {weights!r}")
         states, targets, values = as_device_examples(examples, outcomes=True)
         try:
             policies = as_device_policies(examples)
@@ -279,7 +313,7 @@ class NNetWrapper:
             if target == "visits":
                 raise
             policies = None
-        out = self.yk_net().evaluate(states, targets, values, policies=policies)
+        out = self.yk_net(raw=weights == "raw").evaluate(states, targets, values, policies=policies)
         term = out["policy_ce_soft"] if target == "visits" else out["policy_ce"]
         out["loss"] = term + float(self.args.get("vloss_weight", 1.0)) * out["value_mse"]
         return out
@@ -296,9 +330,13 @@ class NNetWrapper:
         from .train import Trainer
         if getattr(self, "_tr", None) is None:
             a = self.args
+            decay, every = self.ema_knobs()
             self._tr = Trainer(self.nnet.state_dict(), a.hidden, a.nblocks, lr=a.lr, weight_decay=a.weight_decay,
                                max_batch=a.batch_size, vloss_weight=a.get("vloss_weight", 1.0),
-                               dropout=a.dropout, seed=a.get("seed", 0), amp=self.uses_amp())
+                               dropout=a.dropout, seed=a.get("seed", 0), amp=self.uses_amp(),
+                               ema_decay=decay, ema_every=every)
+            if decay > 0.0 and self._ema_sd is not None:  # (averaged weights loaded before there was a trainer)
+                self._tr.load_ema(self._ema_sd, self.ema_updates)
         return self._tr
 
     def _sample_cdf(self, examples, states, targets, values, soft, gamma, sigma):
@@ -360,7 +398,13 @@ class NNetWrapper:
         (its policy KL over the pool's mean KL), the KL of its visit policy from this net's policy as the
         call found the net (one YkNet.evaluate over the un-augmented pool; needs the policies).  The T
         steps are split over args.epochs rounds (round e: steps floor(e T / E) .. floor((e + 1) T / E) - 1;
-        empty rounds are skipped), a round being what an epoch is to the loss report and the symmetries."""
+        empty rounds are skipped), a round being what an epoch is to the loss report and the symmetries.
+
+        args.emaDecay: 0 (default; the net that plays is the last step's iterate, as in the reference) or a decay
+        in (0, 1) - averaged weights, a departure from the reference: after every
+        args.emaEvery-th step (default 1) a device shadow of the parameters moves toward them,
+        e <- e + w_t (p - e).  self.nnet stays the raw iterate; after the call yk_net() - predict, the engines,
+        the gate, reanalysis, evaluate, the sampler's surprise - is built from the shadow."""
         from . import dist as D
         from .replay import as_device_examples, as_device_policies, check_sample_knobs, sample_rounds
         target = self.args.get("policy_target", "argmax")
@@ -371,6 +415,7 @@ class NNetWrapper:
         K.symmetry_flags(symmetries)  # an unknown name: ValueError, before any device work
         T, gamma, sigma = check_sample_knobs(self.args.get("trainSteps", 0) or 0, self.args.get("sampleRecency", 1.0),
                                              self.args.get("sampleSurprise", 0.0))
+        ema_on = self.ema_on()  # (bad emaDecay / emaEvery: ValueError, before any device work)
         tr = self._trainer()
         states, targets, values = as_device_examples(examples)
         # "visits": the same rows' policies as a CSR; "argmax" calls the trainer exactly as before
@@ -433,6 +478,8 @@ class NNetWrapper:
         with torch.no_grad():
             self.nnet.load_state_dict(tr.state_dict())  # the torch copy feeds checkpoints and predict
         self._yk = None
+        if ema_on:  # the shadow's host copy feeds predict and the checkpoints' second set
+            self._set_shadow(tr.ema_state_dict(), tr.ema_state()["updates"])
 
     # ---- checkpoints (NNet.py:198-213): the reference's dict, loaded without unpickling code
     def save_checkpoint(self, folder="checkpoint", filename="checkpoint.pth.tar"):
@@ -443,8 +490,18 @@ class NNetWrapper:
         else:
             opt = torch.optim.AdamW(self.nnet.parameters(), lr=self.args.lr,
                                     weight_decay=self.args.weight_decay).state_dict()
-        torch.save({"state_dict": self.nnet.state_dict(), "optimizer": opt, "args": dict(self.args)},
-                   os.path.join(folder, filename))
+        ck = {"state_dict": self.nnet.state_dict(), "optimizer": opt, "args": dict(self.args)}
+        if self.ema_on():  # "state_dict" stays the raw iterate: the optimiser state belongs to it
+            ck["ema_state_dict"] = OrderedDict((k, v.clone()) for k, v in self.ema_state_dict().items())
+            ck["ema_updates"] = int(self.ema_updates)
+        torch.save(ck, os.path.join(folder, filename))
+
+    def export_ema(self, folder="checkpoint", filename="ema.pth.tar"):
+        """The averaged weights as a plain reference-format checkpoint ({"state_dict", "args"}): the file for
+        bot.py, `python -m yacht_amd.evaluate` or the reference.  Without a shadow these are the raw weights."""
+        os.makedirs(folder, exist_ok=True)
+        sd = OrderedDict((k, v.detach().to("cpu").clone()) for k, v in self.ema_state_dict().items())
+        torch.save({"state_dict": sd, "args": dict(self.args)}, os.path.join(folder, filename))
 
     def load_checkpoint(self, folder="checkpoint", filename="checkpoint.pth.tar", load_optimizer=False):
         from .train import load_optimizer_state_dict
@@ -454,6 +511,13 @@ class NNetWrapper:
         self._yk = None
         if getattr(self, "_tr", None) is not None:
             self._tr.load_params(self.nnet.state_dict())
+        if self.ema_on():  # (off: the file's averaged weights, if any, are ignored)
+            if "ema_state_dict" in ck:
+                self._set_shadow(OrderedDict(ck["ema_state_dict"]), int(ck.get("ema_updates", 0)))
+            else:  # a file without them: the loaded weights are the average of themselves
+                self._set_shadow(None, 0)
+            if getattr(self, "_tr", None) is not None:
+                self._tr.load_ema(self._ema_sd, self.ema_updates)
         if load_optimizer and "optimizer" in ck:
             load_optimizer_state_dict(self._trainer(), self.nnet, ck["optimizer"])
 

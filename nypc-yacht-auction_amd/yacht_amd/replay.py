@@ -147,6 +147,23 @@ def check_sample_knobs(trainSteps=0, sampleRecency=1.0, sampleSurprise=0.0):
     return T, gamma, sigma
 
 
+def check_ema_knobs(emaDecay=0.0, emaEvery=1):
+    """(decay, every) of the averaged weights as (float, int): emaDecay in [0, 1) (0 / unset:
+    off - the net that plays is the raw iterate), emaEvery an int >= 1 (the shadow moves after every emaEvery-th
+    optimiser apply).  ValueError otherwise, and for an emaEvery != 1 while the average is off (it would
+    silently do nothing)."""
+    decay = float(0.0 if emaDecay is None else emaDecay)
+    if not 0.0 <= decay < 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"emaDecay must lie in [0, 1), got {emaDecay!r}")
+    every = 1 if emaEvery is None else emaEvery
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"emaEvery must be an int >= 1, got {emaEvery!r}")
+    if decay == 0.0 and every != 1:
+        raise ValueError("emaEvery needs emaDecay > 0: without it no averaged weights are kept and the interval "
+                         "would do nothing")
+    return decay, int(every)
+
+
 def sample_rounds(trainSteps: int, epochs: int):
     """The trainSteps sampled steps split over `epochs` rounds: [(first step, one past the last)] per round,
     round e = floor(e T / E) .. floor((e + 1) T / E) - 1; empty rounds (T < E) have first == past."""
@@ -493,5 +510,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_playout_knobs", "examples_full_rows", "policies_take", "check_sample_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "augment_examples", "check_playout_knobs", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
            "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]

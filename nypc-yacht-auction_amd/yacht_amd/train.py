@@ -42,7 +42,11 @@ class Trainer:
 
     def __init__(self, state_dict, hidden: int, nblocks: int, lr=2e-3, weight_decay=1e-4, max_batch=512,
                  vloss_weight=1.5, dropout=0.3, seed=0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=5.0,
-                 amp=False, init_scale=65536.0, growth_interval=2000):
+                 amp=False, init_scale=65536.0, growth_interval=2000, ema_decay=0.0, ema_every=1):
+        """ema_decay in (0, 1): keep averaged weights on the device - after every
+        ema_every-th apply a shadow of the flat parameters moves toward them (yk_trainer_set_ema); 0: off."""
+        from .replay import check_ema_knobs
+        ema_decay, ema_every = check_ema_knobs(ema_decay, ema_every)
         self.names = list(state_dict.keys())
         self.shapes = [tuple(t.shape) for t in state_dict.values()]
         arrs = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy()) for t in state_dict.values()]
@@ -58,6 +62,8 @@ class Trainer:
         call("yk_trainer_buffers", self.handle, C.byref(pp), C.byref(gp), C.byref(n))
         self.nparams = int(n.value)
         self._pptr, self._gptr = pp.value, gp.value
+        if ema_decay > 0.0:
+            self.set_ema(ema_decay, ema_every)
 
     # ---- device views (no copies)
     def params(self) -> torch.Tensor:
@@ -65,6 +71,12 @@ class Trainer:
 
     def grads(self) -> torch.Tensor:
         return torch.as_tensor(_DevView(self._gptr, self.nparams), device="cuda")
+
+    def ema(self) -> torch.Tensor:
+        """The averaged weights as a flat device view, laid out as params(); YkError (state) when off."""
+        ep = C.c_void_p()
+        call("yk_trainer_ema_buffer", self.handle, C.byref(ep))
+        return torch.as_tensor(_DevView(ep.value, self.nparams), device="cuda")
 
     # ---- steps
     @staticmethod
@@ -159,6 +171,35 @@ class Trainer:
         arrs = [np.ascontiguousarray(state_dict[k].detach().to("cpu", torch.float32).numpy()) for k in self.names]
         p = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         call("yk_trainer_set", self.handle, 0, p, -1)
+
+    # ---- averaged weights
+    def set_ema(self, decay: float, every: int = 1):
+        """Turn the average on (decay in (0, 1), every >= 1: the shadow starts from the current parameters
+        with count 0; while on, only the two knobs change) or off (decay 0)."""
+        call("yk_trainer_set_ema", self.handle, float(decay), int(every))
+
+    def ema_state_dict(self):
+        """Host copy of the averaged weights in state_dict order."""
+        outs = [np.zeros(s, dtype=np.float32) for s in self.shapes]
+        arr = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        call("yk_trainer_ema_get", self.handle, arr)
+        return OrderedDict((k, torch.from_numpy(o)) for k, o in zip(self.names, outs))
+
+    def load_ema(self, state_dict=None, updates: int = -1):
+        """The shadow from `state_dict`, or from the current parameters (a device copy) when it is None;
+        updates >= 0 also sets the count of updates made."""
+        if state_dict is None:
+            call("yk_trainer_ema_set", self.handle, None, int(updates))
+            return
+        arrs = [np.ascontiguousarray(state_dict[k].detach().to("cpu", torch.float32).numpy()) for k in self.names]
+        p = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        call("yk_trainer_ema_set", self.handle, p, int(updates))
+
+    def ema_state(self) -> dict:
+        """decay, every, updates made and applies since the last update; all zero when off."""
+        out = np.zeros(4, dtype=np.float64)
+        call("yk_trainer_ema_state", self.handle, out.ctypes.data)
+        return {"decay": float(out[0]), "every": int(out[1]), "updates": int(out[2]), "since": int(out[3])}
 
     def close(self):
         if getattr(self, "handle", None):
