@@ -351,6 +351,33 @@ int yk_engine_set_playout_cap(yk_engine_t* eng, int fast_sims, double full_prob)
  * env_base) is a full move under full_prob, else 0, m = 0 .. n_moves-1.  NULL full, n_moves < 0, full_prob
  * outside [0, 1] or NaN: YK_ERR_ARG.  Host only. */
 int yk_playout_schedule(uint64_t seed, uint32_t env_base, double full_prob, int n_moves, uint8_t* full /* HOST */);
+/* Forced playouts and policy target pruning (KataGo, Wu 2019 section 3.2), a departure from the reference,
+ * opt-in; DESIGN.md section 6f.  Off (k = 0, the state of a new engine): nothing changes.  On (k > 0), at the
+ * root (depth 0) of every FULL move of yk_selfplay - a fast move of the playout cap is neither forced nor
+ * pruned, the rule of the root noise; yk_arena, yk_mcts_search and interior nodes never are.  Doubles unless
+ * it says float; Ns the root's visit count, P[a] the float prior the search uses (the noised one under root
+ * noise), N[a] / Q[a] the edge's count and value, c = cpuct:
+ *   Forcing, at every simulation's root pick: a visited edge (N > 0) with N * N < (k * P) * Ns has u = +inf;
+ *     nothing else in the scan changes (the first maximum in ascending action order wins).
+ *   Pruning (prune = 1), once after the move's last simulation: c* = the visited edge with the largest N (the
+ *     lowest action among equals) keeps its count; PUCT* = Q[c*] + (c * P[c*]) * sqrt(Ns) / (1 + N[c*]).  Every
+ *     other visited edge: f = the largest integer with f * f <= (k * P) * Ns; from n = N, n is decremented
+ *     while n > 0, N - n < f and Q + (c * P) * sqrt(Ns) / (1 + (n - 1)) < PUCT*; an n brought to exactly 1 that
+ *     way becomes 0.  The pruned counts are what the move's record holds (visits, info[5]; edges at 0 leave the
+ *     list) and what the real move is drawn from under both temperature rules; info[4] stays the raw Ns, and
+ *     the tree keeps its raw N and Q.  The record image and its size are unchanged.
+ * prune = 0 forces without pruning (tests, ablation).  Lives in the engine, not in yk_engine_config_t.
+ * k < 0, NaN or infinite, or prune outside {0, 1}: YK_ERR_ARG, the engine unchanged.  Touches no device memory. */
+int yk_engine_set_forced_playouts(yk_engine_t* eng, double k, int prune);
+/* The pruning alone, on n rows given as a CSR: DEVICE indptr[n + 1], and per entry cols (the action), counts
+ * (N; an entry with N <= 0 is no visited edge and keeps its word), q (Q), p (P); per row ns[n] (Ns, negative
+ * taken as 0) -> DEVICE out[nnz], the pruned counts (out is none of the inputs).  c* of a row: the largest count, the
+ * lowest column among equals.  k = 0 copies.  One wavefront per row; no atomics on data; equal inputs give
+ * equal bits.  A NULL pointer, n < 0, k negative, NaN or infinite: YK_ERR_ARG before anything touches the
+ * device.  An indptr that starts below 0 or decreases (or a row of more than 2^31 - 1 entries), detected on the
+ * device before any row is read: YK_ERR_RANGE, out untouched.  Synchronises `stream`. */
+int yk_policy_prune(const int64_t* indptr, const int32_t* cols, const int32_t* counts, const double* q, const float* p,
+                    const int32_t* ns, int64_t n, double k, double cpuct, int32_t* out, void* stream);
 /* Per-kernel timing with HIP events on the engine's stream; resets the accumulators.
  * enable = 0 off, k > 0 on: the per-move launches are timed every time, the per-simulation
  * forward / expand pair in every k-th simulation of a move (1 = all; an event record between
@@ -373,7 +400,9 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env)
  * 1-3 expansions whose prior took the window, the sparse and the general path (their sum: stats 0;
  *   YK_PRIOR_FAST=0 sends every one through the general path)
- * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena) */
+ * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena)
+ * 5 root picks of the last batch that took a forced edge, 6 visits its pruning took off the recorded counts
+ *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena) */
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)

@@ -25,6 +25,7 @@
 #include "yk_api.h"
 #include "yk_common.h"
 #include "yk_engine_dev.h"
+#include "yk_forced.h"
 #include "yk_net.h"
 
 #define YK_MAX_GROUPS 8
@@ -337,9 +338,14 @@ __global__ __launch_bounds__(256) void k_move_begin(EngDev d, int move, int exte
 // full scan, so the same winner, bit for bit.  Returns the winner's compact index (0x7FFFFFFF: none)
 // and its edge tag (0: unvisited), or -1 when the order's nk stored entries end before the walk does
 // (the caller then scans the whole set); `scanned` counts the entries read.
+// FORCED (a full self-play move with forced playouts): a visited edge that forced_edge names
+// has u = +inf - only the visited list changes, an unvisited edge is never forced - and `fpick` is set when
+// such an edge is the winner.
+template <bool FORCED>
 __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint32_t nv, const float* P,
                                          const uint16_t* S, const Edge* edges, int V, int nk, int ws, float sq,
-                                         float sqe, uint32_t& wtag, uint64_t& scanned, uint64_t& gathered) {
+                                         float sqe, uint32_t& wtag, uint64_t& scanned, uint64_t& gathered,
+                                         uint32_t Ns, double fk, int& fpick) {
     const uint16_t* oj = d.ro_j + (long)t * RO_K;
     const float* op = d.ro_p + (long)t * RO_K;
     const uint32_t* rv = d.rv + (long)t * RV_CAP;
@@ -355,7 +361,8 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
         const int j = (int)(w & 0xFFFu);
         const float p = P[j];
         const Edge ev = edges[(w >> 12) - 1];
-        const float u = (float)ev.Q + ((d.c32 * p) * sq) / (float)(ev.N + 1);
+        float u = (float)ev.Q + ((d.c32 * p) * sq) / (float)(ev.N + 1);
+        if (FORCED && forced_edge(ev.N, p, Ns, fk)) u = INFINITY;
         if (u > best || (u == best && j < bj)) {
             best = u;
             bj = j;
@@ -410,6 +417,7 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
     }
     const int mine = bj;
     wave_argmax_step(best, bj);
+    if (FORCED) fpick = best == INFINITY;  // (no other u is +inf: Q, P and the square roots are finite)
     const uint64_t own = __ballot(mine == bj);  // the lane whose own candidate won holds its tag
     wtag = own ? __builtin_amdgcn_readlane(btag, (int)__builtin_ctzll(own)) : 0u;
     scanned += (uint64_t)nv + (uint64_t)walked;
@@ -432,6 +440,11 @@ __device__ __forceinline__ void select_none(const EngDev& d, int e, int lane) {
 // would put two more dependent round trips on every simulation's chain.
 // All 64 lanes of the game's wave call it together.
 //
+// FORCED: the forced playouts of DESIGN.md s6f at depth 0, on every path the root's pick can take - root_scan's
+// visited list, and the full scan (a move's first simulation, root_scan's -1, a visited list that overflowed,
+// YK_ROOT_SCAN=0).  The node summary needs no case of its own: it decides a node only at Ns = 0, where no
+// edge is visited, and only visited edges are forced.  The default instantiation is the code it was.
+//
 // Invariant (no node is terminal): the key of every node record is a state with game_ended == 0.
 // The one writer of a new record is the expansion of a leaf, and a descent flags a leaf only after
 // that state's Es test below came out 0; k_move_begin's compaction copies records unchanged, and the
@@ -440,8 +453,12 @@ __device__ __forceinline__ void select_none(const EngDev& d, int e, int lane) {
 // root (root_c: set after a lookup that followed the test) or a cached child (an edge tag: the backup
 // caches only ids of records, the next level's node, the new leaf or a node without valid actions;
 // after a terminal break end_id is 0 and nothing is cached) - needs no Es test and no lookup.
+template <bool FORCED>
 __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, int t, int g, const uint32_t* env_ids,
-                                            uint64_t* ctr_arr) {
+                                            uint64_t* ctr_arr, const ForcedDev& fd) {
+    // FORCED: 1 when the root's pick was a forced edge.  (Declared first: among the locals below it reorders two
+    // phi nodes of the default instantiation, and the register allocation with them.)
+    int fpick = 0;
     YkS s = ld_state(d.root + e);
     Stream rs{d.seed, env_ids[e], ctr_arr[e]};
     const NodeRec* nodes = d.nodes[g] + (long)t * d.NCAP;
@@ -482,11 +499,12 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
         }
         if (rid != 0 && uni(rc1.z) != RV_OFF) {  // k_root_sort ran this move: root_c holds the root
             const float sq = (float)sqrt((double)f.Ns), sqe = (float)sqrt((double)f.Ns + 1e-8);
-            pre_bj = __builtin_amdgcn_readfirstlane(root_scan(d, t, lane, rc1.z, Pbase + rc.y, Sbase + rc.y, edges,
-                                                              (int)rc.z, (int)rc.w, (int)rc1.w, sq, sqe, pre_tag, scanned,
-                                                              gathered));
+            pre_bj = __builtin_amdgcn_readfirstlane(root_scan<FORCED>(d, t, lane, rc1.z, Pbase + rc.y, Sbase + rc.y, edges,
+                                                                      (int)rc.z, (int)rc.w, (int)rc1.w, sq, sqe, pre_tag,
+                                                                      scanned, gathered, f.Ns, fd.k, fpick));
             pre_tag = __builtin_amdgcn_readfirstlane(pre_tag);
             pre = pre_bj != -1;
+            if (FORCED) fpick = pre ? __builtin_amdgcn_readfirstlane(fpick) : 0;
         }
     }
     while (true) {
@@ -576,6 +594,7 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
                         const float cp = d.c32 * pv[t];
                         if (sv[t]) {
                             u = (float)ev[t].Q + (cp * sq) / (float)(ev[t].N + 1);
+                            if (FORCED && depth == 0 && forced_edge(ev[t].N, pv[t], Ns, fd.k)) u = INFINITY;
                         } else {
                             u = cp * sqe;
                         }
@@ -588,6 +607,7 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
                 }
             }
             if (Vs) wave_argmax_step(best, bj);  // (a stored pick: every lane holds it)
+            if (FORCED && depth == 0) fpick = best == INFINITY;
             scanned += (uint64_t)Vs;
             bj_out = bj;
             // the winner's lane holds its tag: its own best is the wave's (lowest j among equals)
@@ -642,11 +662,19 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
         atomicAdd(gs + 1, (unsigned long long)scanned);
         atomicAdd(gs + 2, (unsigned long long)depth);
         atomicAdd(gs + 7, 1ull);
+        if (FORCED) atomicAdd(gs + 12, (unsigned long long)fpick);
         atomicAdd(gs + 8, (unsigned long long)gathered);
     }
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr) {
+// FD: ForcedDev for the FORCED instantiation (the launches of a full self-play move with forced playouts) and
+// nothing for the default one, whose arguments - and with them its code - are what they were without the
+// feature (one more argument, even unread, changes the register allocation).
+__device__ __forceinline__ ForcedDev forced_arg() { return ForcedDev{0.0, 0.0}; }
+__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd) { return fd; }
+template <bool FORCED, class... FD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
+    static_assert(sizeof...(FD) == (FORCED ? 1 : 0), "ForcedDev with FORCED, else no further argument");
     const int lane = threadIdx.x & 63;
     // the wave's game as a scalar: every per-game base address is then scalar arithmetic, which keeps
     // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
@@ -658,15 +686,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
     const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
-    select_game(d, e, lane, t, g, env_ids, ctr_arr);
+    select_game<FORCED>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...));
 }
 
 // Leaf expansion (MCTS.py:84-115) and backup (MCTS.py:154-164) of this simulation, then -
 // when do_select - the next simulation's descent for the same game (one kernel boundary per
 // simulation fewer).  One wave per game.
 __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane, int t, int g);
+template <bool FORCED, class... FD>  // (FD: as k_select)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
-    EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr) {
+    EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
+    static_assert(sizeof...(FD) == (FORCED ? 1 : 0), "ForcedDev with FORCED, else no further argument");
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
@@ -682,7 +712,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_W
             return;
         }
         wave_sync();  // this wave's backup writes (edges, slots, Ns) precede its descent's reads
-        select_game(d, e, lane, t, g, env_ids, ctr_arr);
+        select_game<FORCED>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...));
     }
 }
 
@@ -1201,7 +1231,12 @@ __global__ __launch_bounds__(256) void k_root_sort(EngDev d) {
 
 // getActionProb tail (MCTS.py:40-54) + Coach sampling/step (Coach.py:59-72).  One wave per game.
 // kind: 0, or YK_REC_FAST for a fast move of the playout cap (ORed into the record's status word).
-__global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind) {
+// PRUNE (a full self-play move with forced playouts and pruning on): the gathered list is
+// pruned in LDS before it is recorded and drawn from - the tree keeps its raw N and Q, info[4] the raw Ns.
+template <bool PRUNE, class... FD>  // (FD: as k_select)
+__global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, FD... fdp) {
+    static_assert(sizeof...(FD) == (PRUNE ? 1 : 0), "ForcedDev with PRUNE, else no further argument");
+    const ForcedDev fd = forced_arg(fdp...);
     __shared__ uint32_t vis_all[GAMES_PER_BLOCK][ASIZE];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int e = d.e_lo + blockIdx.x * GAMES_PER_BLOCK + w;
@@ -1246,10 +1281,55 @@ __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind) 
                 const uint64_t bal = __ballot(sl[b] != 0);
                 if (sl[b]) {
                     const int pos = nvis + __popcll(bal & ((1ull << lane) - 1));
-                    vis[pos] = ((uint32_t)compact_to_action(vi, j) << 16) | (n[b] & 0xFFFF);
+                    // (PRUNE: the compact index for now - the pruning needs the edge's P and slot)
+                    vis[pos] = ((uint32_t)(PRUNE ? j : compact_to_action(vi, j)) << 16) | (n[b] & 0xFFFF);
                 }
                 nvis += __popcll(bal);
             }
+        }
+        if (PRUNE && nvis > 0) {
+            // policy target pruning: lanes stride the visited edges.  The best child c* - the largest N, the
+            // lowest action among equals (the list ascends in action) - keeps its count and sets the bound
+            const float* P = d.arenaP + (long)t * d.AE + nd.p_off;
+            wave_sync();
+            int bn = -1, bi = 0x7FFFFFFF;
+            for (int i = lane; i < nvis; i += 64) {
+                const int c = (int)(vis[i] & 0xFFFF);
+                if (c > bn) {
+                    bn = c;
+                    bi = i;
+                }
+            }
+            wave_argmax_step(bn, bi);
+            const int jb = (int)(vis[bi] >> 16);
+            const Edge eb = edges[S[jb] - 1];
+            const double pstar = puct_value(eb.Q, P[jb], root_ns, fd.c, eb.N);
+            // every other edge's pruned count; the edges left without a visit leave the list, which is
+            // compacted in place a piece of 64 at a time (a piece is read whole before any of it is written,
+            // and the writes land at or before the entries read)
+            int out = 0;
+            uint32_t cut = 0;
+            for (int i0 = 0; i0 < nvis; i0 += 64) {
+                const int i = i0 + lane;
+                uint32_t word = 0;
+                bool keep = false;
+                if (i < nvis) {
+                    const int j = (int)(vis[i] >> 16);
+                    const Edge ev = edges[S[j] - 1];
+                    const uint32_t n = i == bi ? ev.N : pruned_count(ev.N, ev.Q, P[j], root_ns, fd.k, fd.c, pstar);
+                    cut += ev.N - n;
+                    keep = n > 0;
+                    word = ((uint32_t)compact_to_action(vi, j) << 16) | (n & 0xFFFF);
+                }
+                const uint64_t bal = __ballot(keep);
+                wave_sync();
+                if (keep) vis[out + __popcll(bal & ((1ull << lane) - 1))] = word;
+                out += __popcll(bal);
+            }
+            nvis = out;
+            cut = (uint32_t)xlane_sum((int)cut);
+            if (lane == 0 && cut)
+                atomicAdd(reinterpret_cast<unsigned long long*>(d.gstats + (long)e * GST) + 13, (unsigned long long)cut);
         }
     } else if (lane == 0) {
         atomicOr(d.err, ERR_ROOT);
@@ -1456,6 +1536,8 @@ struct yk_engine {
     int fast_sims = 0;           // playout cap (yk_engine_set_playout_cap; 0: off): a fast move's simulations
     double full_prob = 1.0;      // and the probability that a move of a yk_selfplay batch is a full one
     int64_t fast_moves = 0;      // lock-step moves of the last batch that ran with the fast cap
+    double forced_k = 0.0;       // forced playouts (yk_engine_set_forced_playouts; 0: off) at the self-play roots
+    bool forced_prune = true;    // of full moves, and whether k_move_end prunes the move's counts
     yk_engine() = default;
     yk_engine(const yk_engine&) = delete;
     yk_engine& operator=(const yk_engine&) = delete;
@@ -1547,10 +1629,25 @@ int check_errors(yk_engine* eng, hipStream_t s) {
 // noise_move >= 0 (self-play with root noise): that move's roots are noised - k_root_noise phase 0
 // before the first descent, phase 1 after simulation 0's expansion, which then ends without the
 // fused descent whatever the root-scan mode.  -1: no noise launch is made.
+// forced (a full self-play move with forced playouts): the descents are the FORCED
+// instantiations; every other caller runs the default ones, whose code the feature leaves as it was.
 int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint32_t* env_ids, uint64_t* ctr,
-             int noise_move = -1) {
+             int noise_move = -1, const ForcedDev* forced = nullptr) {
     const dim3 bb(256);
     if (sims <= 0) return YK_OK;
+    const auto select = [&](const EngDev& dd, hipStream_t s) {
+        if (forced)
+            hipLaunchKernelGGL((k_select<true, ForcedDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced);
+        else
+            hipLaunchKernelGGL((k_select<false>), game_grid(dd), bb, 0, s, dd, env_ids, ctr);
+    };
+    const auto expand_backup = [&](const EngDev& dd, hipStream_t s, int do_select) {
+        if (forced)
+            hipLaunchKernelGGL((k_expand_backup<true, ForcedDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr,
+                               *forced);
+        else
+            hipLaunchKernelGGL((k_expand_backup<false>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr);
+    };
     EngDev dg[YK_MAX_GROUPS];
     for (int g = 0; g < G; g++) {
         dg[g] = G == 1 ? eng->d : group_dev(eng, g);
@@ -1560,7 +1657,7 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
             if (rc) return rc;
         }
         prof_mark(eng, g, KC_SELECT, st[g]);  // the first descent; later ones run in k_expand_backup's tail
-        hipLaunchKernelGGL(k_select, game_grid(dg[g]), bb, 0, st[g], dg[g], env_ids, ctr);
+        select(dg[g], st[g]);
         YK_LAUNCHED();
     }
     for (int k = 0; k < sims; k++) {
@@ -1597,11 +1694,10 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
             const bool sort_root = k == 0 && sims > 1 && eng->root_scan;
             const bool noise = k == 0 && noise_move >= 0;  // the roots simulation 0 has just expanded
             const bool fuse = k + 1 < sims && !sort_root && !noise;  // the next descent in the expand's tail
-            hipLaunchKernelGGL(k_expand_backup, game_grid(d), bb, 0, st[g], d, fuse && !eng->split_descent ? 1 : 0,
-                               env_ids, ctr);
+            expand_backup(d, st[g], fuse && !eng->split_descent ? 1 : 0);
             YK_LAUNCHED();
             if (fuse && eng->split_descent) {
-                hipLaunchKernelGGL(k_select, game_grid(d), bb, 0, st[g], d, env_ids, ctr);
+                select(d, st[g]);
                 YK_LAUNCHED();
             }
             if (noise) {
@@ -1610,7 +1706,7 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
                 if (rc) return rc;
                 if (!sort_root && k + 1 < sims) {  // the second descent on its own, as after k_root_sort
                     prof_mark(eng, g, KC_SCAN, st[g]);
-                    hipLaunchKernelGGL(k_select, game_grid(d), bb, 0, st[g], d, env_ids, ctr);
+                    select(d, st[g]);
                     YK_LAUNCHED();
                 }
             }
@@ -1618,7 +1714,7 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
                 if (timed) prof_mark(eng, g, KC_SCAN, st[g]);
                 hipLaunchKernelGGL(k_root_sort, dim3((unsigned)(d.e_hi - d.e_lo)), bb, 0, st[g], d);
                 YK_LAUNCHED();
-                hipLaunchKernelGGL(k_select, game_grid(d), bb, 0, st[g], d, env_ids, ctr);
+                select(d, st[g]);
                 YK_LAUNCHED();
             }
             if (timed && eng->prof_stride > 1) prof_mark(eng, g, -1, st[g]);  // untimed sims follow
@@ -1862,6 +1958,9 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
     const bool capped = eng->fast_sims > 0 && !d.arena;  // nor are they ever capped
     eng->have_priors = false;
     eng->fast_moves = 0;
+    // forced playouts and pruning: self-play only, and (below) full moves only - the rule of the root noise
+    const bool forcing = eng->forced_k > 0.0 && !d.arena;
+    const ForcedDev fd{eng->forced_k, eng->cfg.cpuct};
     if (root_values)  // info[..][7] = 0 also past a game's end: a zero word is "no value recorded"
         YK_HIP(hipMemsetAsync(d.rec_info, 0, sizeof(int32_t) * (size_t)d.E * d.M * 8, s));
     if (noise && eng->nz.prior_after) {  // dense by action: 0 off the valid set and past the game's end
@@ -1886,12 +1985,17 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
         const bool fast = capped && !playout_full(seed, env_base, move, eng->full_prob);
         eng->fast_moves += fast;
         if (!d.arena || d.arena_agent == YK_PLAYER_MCTS || d.arena_opp == YK_PLAYER_MCTS) {
-            int rc = run_sims(eng, G, st, fast ? eng->fast_sims : d.sims, d.env_id, d.ctr, noise && !fast ? move : -1);
+            int rc = run_sims(eng, G, st, fast ? eng->fast_sims : d.sims, d.env_id, d.ctr, noise && !fast ? move : -1,
+                              forcing && !fast ? &fd : nullptr);
             if (rc) return rc;
         }
         for (int g = 0; g < G; g++) {
             prof_mark(eng, g, KC_MOVE_END, st[g]);
-            hipLaunchKernelGGL(k_move_end, game_grid(dg[g]), bb, 0, st[g], dg[g], move, fast ? YK_REC_FAST : 0);
+            if (forcing && !fast && eng->forced_prune)
+                hipLaunchKernelGGL((k_move_end<true, ForcedDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move, 0, fd);
+            else
+                hipLaunchKernelGGL((k_move_end<false>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
+                                   fast ? YK_REC_FAST : 0);
             YK_LAUNCHED();
             if (root_values) {  // the games with nmoves == move + 1; root[e] is still this move's root
                 prof_mark(eng, g, KC_ROOT_VALUE, st[g]);
@@ -1936,6 +2040,13 @@ int yk_engine_set_playout_cap(yk_engine_t* eng, int fast_sims, double full_prob)
         return YK_ERR_ARG;
     eng->fast_sims = fast_sims;
     eng->full_prob = full_prob;
+    return YK_OK;
+}
+
+int yk_engine_set_forced_playouts(yk_engine_t* eng, double k, int prune) {
+    if (!eng || !(k >= 0.0) || std::isinf(k) || (prune != 0 && prune != 1)) return YK_ERR_ARG;  // (NaN fails k >= 0)
+    eng->forced_k = k;
+    eng->forced_prune = prune != 0;
     return YK_OK;
 }
 
@@ -2067,12 +2178,15 @@ int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n) {
     std::vector<uint64_t> gs((size_t)d.E * GST);
     YK_HIP(hipDeviceSynchronize());
     YK_HIP(hipMemcpy(gs.data(), d.gstats, sizeof(uint64_t) * gs.size(), hipMemcpyDeviceToHost));
-    int64_t c[4] = {0, 0, 0, 0};  // scan edges; expansions by prior path: window, sparse, general
+    // scan edges; expansions by prior path: window, sparse, general; the playout cap's fast moves; root picks
+    // that took a forced edge and visits the pruning took off the recorded counts
+    int64_t c[7] = {0, 0, 0, 0, eng->fast_moves, 0, 0};
     for (int e = 0; e < d.E; e++) {
         c[0] += (int64_t)gs[(size_t)e * GST + 8];
         for (int k = 0; k < 3; k++) c[1 + k] += (int64_t)gs[(size_t)e * GST + 9 + k];
+        for (int k = 0; k < 2; k++) c[5 + k] += (int64_t)gs[(size_t)e * GST + 12 + k];
     }
-    for (int i = 0; i < n; i++) out[i] = i < 4 ? c[i] : (i == 4 ? eng->fast_moves : 0);  // 4: playout-cap fast moves
+    for (int i = 0; i < n; i++) out[i] = i < 7 ? c[i] : 0;
     return YK_OK;
 }
 

@@ -21,7 +21,8 @@ _ERR_NAMES = {YK_ERR_ARG: "bad argument", YK_ERR_HIP: "HIP error", YK_ERR_NOMEM:
               YK_ERR_CAPACITY: "engine capacity exceeded", YK_ERR_STATE: "engine state error",
               YK_ERR_RANGE: "a value outside the range the operation accepts (a net weight with |w| >= 65520, "
                             "the fp16 split's range; sampling weights negative, NaN or without a finite positive total; "
-                            "splice rows not strictly ascending within the CSR; a take index outside the CSR)"}
+                            "splice rows not strictly ascending within the CSR; a take index outside the CSR; "
+                            "row pointers that start below 0 or decrease)"}
 YK_REC_FAST = 0x100  # info[..., 6] of a fast move of the playout cap: the step status | this bit
 YK_NET_ERR_SYNC = 1  # yk_net_errors: a value-head wave timed out on the v_head.2 hand-off
 
@@ -132,6 +133,8 @@ SIGNATURES = {
     "yk_playout_schedule": [U64, U32, C.c_double, I, P],
     "yk_examples_full_rows": [P, I, I, I, I, C.c_int64, P, C.c_int64, P, P],
     "yk_policies_take": [P, P, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, P],
+    "yk_engine_set_forced_playouts": [P, C.c_double, I],
+    "yk_policy_prune": [P, P, P, P, P, P, C.c_int64, C.c_double, C.c_double, P, P],
     "yk_ema_weight": [C.c_double, C.c_int64, P],
     "yk_ema_update": [P, P, C.c_int64, C.c_float, P],
     "yk_trainer_set_ema": [P, C.c_double, I],
@@ -144,15 +147,16 @@ _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_re
             "yk_trainer_step_count": C.c_int64}
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
-# search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap and the
-# averaged weights (A/B baselines may predate them)
+# search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap, the
+# averaged weights and the forced playouts (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
           "yk_sample_draw", "yk_reanalyse_select", "yk_policies_from_counts", "yk_policies_splice",
           "yk_engine_root_prior", "yk_engine_set_playout_cap", "yk_playout_schedule", "yk_examples_full_rows",
           "yk_policies_take", "yk_ema_weight", "yk_ema_update", "yk_trainer_set_ema", "yk_trainer_ema_buffer",
-          "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state"}
+          "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state", "yk_engine_set_forced_playouts",
+          "yk_policy_prune"}
 _lib = None
 
 

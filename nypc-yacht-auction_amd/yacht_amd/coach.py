@@ -18,6 +18,10 @@ any number of ranks (one process per GPU, torch.distributed):
 * playout cap randomization (opt-in, ``args.playoutFastSims`` / ``playoutFullProb``; not in the reference;
   DESIGN.md 6e): each move of a self-play batch is searched in full (numMCTSSims) with probability
   playoutFullProb and with playoutFastSims simulations otherwise; only the full moves become examples.
+* forced playouts and policy target pruning (opt-in, ``args.forcedPlayoutsK``, ``forcedPrune``; not in the
+  reference): at the roots of self-play's full moves a visited child is searched until
+  N^2 >= k P Ns, and the forced visits the search's PUCT values did not justify are taken off the recorded
+  counts, which the policy targets are made of.
 * held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
   iteration that never enter training, on which the previous and the new net are evaluated after
   train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
@@ -96,11 +100,17 @@ class Coach:
         from .replay import check_playout_knobs
         self.playout_fast_sims, self.playout_full_prob = check_playout_knobs(
             args.get("playoutFastSims", None), args.get("playoutFullProb", None), args.get("numMCTSSims", None))
+        # forced playouts and policy target pruning at the self-play roots.  Unset: off
+        from .replay import check_forced_knobs
+        self.forced_k, self.forced_prune = check_forced_knobs(args.get("forcedPlayoutsK", None),
+                                                              args.get("forcedPrune", None))
         # averaged weights: NNetWrapper's knobs, checked here as well.  With emaDecay set the
         # net that plays, gates and reanalyses is the averaged one (NNetWrapper.yk_net); learn's flow is unchanged
         from .replay import check_ema_knobs
         self.ema_decay, self.ema_every = check_ema_knobs(args.get("emaDecay", 0.0), args.get("emaEvery", 1))
-        self.last_selfplay = None  # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims)
+        # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims); with forcedPlayoutsK also
+        # {"forced_picks", "pruned_visits"} (this rank's)
+        self.last_selfplay = None
         self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
         self.holdout_eps = int(args.get("holdoutEps", 0) or 0)
@@ -136,7 +146,9 @@ class Coach:
                               # each move's root value in the records, only when the value targets use it
                               record_root_values=self._value_targets_on(),
                               # the playout cap; the held-out games are played under the same config
-                              playout_fast_sims=self.playout_fast_sims, playout_full_prob=self.playout_full_prob)
+                              playout_fast_sims=self.playout_fast_sims, playout_full_prob=self.playout_full_prob,
+                              # forced playouts and pruning; again the same for the held-out games
+                              forced_playouts_k=self.forced_k, forced_prune=self.forced_prune)
 
     def _value_targets_on(self) -> bool:
         return (self.value_mix, self.value_lambda) != (0.0, 1.0)
@@ -165,7 +177,8 @@ class Coach:
         try:
             eng.run(self.game.rng.seed, base + lo)
             img = eng.pack_records()
-            sims_run = eng.stats()["sims"]
+            st = eng.stats()
+            sims_run = st["sims"]
         finally:
             eng.close()
         gathered = D.allgather_records(img)
@@ -173,8 +186,12 @@ class Coach:
                                      value_mix=self.value_mix, value_lambda=self.value_lambda,
                                      full_only=self.playout_fast_sims > 0)
         self.last_selfplay = dict(searched=shard.n_searched, kept=len(shard), sims=sims_run)
-        log.info("SELF-PLAY %d moves searched, %d examples kept, %d lock-step sims run (this rank)"
-                 % (shard.n_searched, len(shard), sims_run))
+        forced = ""
+        if self.forced_k > 0:
+            self.last_selfplay.update(forced_picks=st["forced_picks"], pruned_visits=st["pruned_visits"])
+            forced = ", %d forced root picks, %d visits pruned" % (st["forced_picks"], st["pruned_visits"])
+        log.info("SELF-PLAY %d moves searched, %d examples kept, %d lock-step sims run (this rank)%s"
+                 % (shard.n_searched, len(shard), sims_run, forced))
         return shard
 
     def reanalyseWindow(self, iteration: int):

@@ -24,7 +24,7 @@ class SelfPlayEngine:
                  max_expansions: int = 0, arena_entries: int = 0, record_stride: int = 1, groups: int = 0,
                  dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
                  dirichlet_eps: float = 0.0, record_root_values: bool = False, playout_fast_sims: int = 0,
-                 playout_full_prob: float = 1.0):
+                 playout_full_prob: float = 1.0, forced_playouts_k: float = 0.0, forced_prune: bool = True):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -52,6 +52,16 @@ class SelfPlayEngine:
         if self.playout_fast_sims != 0:
             try:
                 call("yk_engine_set_playout_cap", self.handle, self.playout_fast_sims, self.playout_full_prob)
+            except Exception:
+                self.close()
+                raise
+        # forced playouts and policy target pruning at the roots of run()'s full moves (never in arena(); DESIGN.md
+        # 6f): a visited root child is searched until N^2 >= k P Ns, and the visits that the search's own PUCT
+        # values did not justify are taken off the recorded counts (forced_prune=False: forcing alone); 0 is off
+        self.forced_playouts_k, self.forced_prune = float(forced_playouts_k), bool(forced_prune)
+        if self.forced_playouts_k != 0.0:
+            try:
+                call("yk_engine_set_forced_playouts", self.handle, self.forced_playouts_k, int(self.forced_prune))
             except Exception:
                 self.close()
                 raise
@@ -125,7 +135,10 @@ class SelfPlayEngine:
                   "forward_parts")
     # yk_engine_counters: the scans' edge gathers; expansions by the prior's path
     # fast_moves: the lock-step moves of the last batch that ran with the fast playout cap
-    COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general", "fast_moves")
+    # forced_picks / pruned_visits: the last batch's root picks that took a forced edge, and the visits the
+    # pruning took off its recorded counts
+    COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general", "fast_moves", "forced_picks",
+                     "pruned_visits")
 
     def stats(self) -> dict:
         out = np.zeros(16, dtype=np.int64)

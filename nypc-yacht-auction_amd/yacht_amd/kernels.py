@@ -419,11 +419,41 @@ def policies_take(policies, idx):
     return out_ip, out_cols, out_vals
 
 
+# ---------------------------------------------------------------- policy target pruning
+def policy_prune(indptr, cols, counts, q, p, ns, k: float, cpuct: float, stream=None):
+    """Policy target pruning of rows of root counts (yk_policy_prune), the rule k_move_end applies after a forced
+    move: device tensors indptr int64 [n + 1], and per entry cols int32 (the action), counts int32 (N), q
+    float64 (Q), p float32 (P); ns int32 [n] (each row's root visit count); k the forced-playouts knob and cpuct
+    the search's.  Returns the pruned counts as a new device int32 tensor; the best child of a row (the largest
+    count, the lowest column among equals) keeps its count, k = 0 copies.  ValueError for row pointers that
+    start below 0 or decrease.  Synchronises."""
+    want = ((indptr, torch.int64), (cols, torch.int32), (counts, torch.int32), (q, torch.float64),
+            (p, torch.float32), (ns, torch.int32))
+    for t, dt in want:
+        if t.dtype != dt or t.dim() != 1:
+            raise TypeError("policy_prune takes vectors: indptr int64, cols / counts / ns int32, q float64, p float32")
+    n = int(indptr.numel()) - 1
+    if n < 0 or int(ns.numel()) != n or not (cols.numel() == counts.numel() == q.numel() == p.numel()):
+        raise ValueError("policy_prune: indptr has n + 1 entries, ns n, and cols / counts / q / p one per edge")
+    out = torch.empty_like(counts)
+    # (an empty CSR's tensors may have no storage: any non-null pointer does, nothing is read or written there)
+    spare = torch.empty(2, dtype=torch.int64, device="cuda")
+    a = [ptr(t) or ptr(spare) for t in (cols, counts, q, p, ns)]
+    try:
+        call("yk_policy_prune", ptr(indptr), a[0], a[1], a[2], a[3], a[4], n, float(k), float(cpuct),
+             ptr(out) or ptr(spare[1:]), stream_ptr(stream))
+    except _lib.YkError as err:
+        if err.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError("policy_prune: indptr must start at >= 0 and never decrease") from None
+    return out
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
            "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice",
-           "examples_full_rows", "policies_take", "_lib"]
+           "examples_full_rows", "policies_take", "policy_prune", "_lib"]
 
 
 def greedy_action(states):

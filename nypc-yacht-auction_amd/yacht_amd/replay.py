@@ -22,6 +22,7 @@ from ._lib import YK_ERR_STATE, YK_OK, YkError, call, lib, stream_ptr
 from .kernels import augment_examples  # (a random symmetry of every example; listed with the buffer's functions)
 from .kernels import policies_from_counts, policies_splice, reanalyse_select  # (the reanalysis' device calls)
 from .kernels import examples_full_rows, policies_take  # (the playout cap's: the full moves' examples)
+from .kernels import policy_prune  # (policy target pruning on rows of counts)
 
 
 def _vcap(max_moves: int, sims: int) -> int:
@@ -145,6 +146,26 @@ def check_sample_knobs(trainSteps=0, sampleRecency=1.0, sampleSurprise=0.0):
         raise ValueError("sampleRecency / sampleSurprise need trainSteps > 0: without it training runs "
                          "epochs of full permutations and the weights would do nothing")
     return T, gamma, sigma
+
+
+def check_forced_knobs(forcedPlayoutsK=None, forcedPrune=None):
+    """(k, prune) of the forced playouts and the policy target pruning as (float, bool):
+    forcedPlayoutsK unset or 0 is off, else a finite number > 0 (KataGo uses 2); forcedPrune (default True)
+    a bool - False forces without pruning the recorded counts, for ablation.  ValueError otherwise, and for
+    forcedPrune=False while the forcing is off (it would silently do nothing)."""
+    k = 0.0 if forcedPlayoutsK is None else forcedPlayoutsK
+    if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)):
+        raise ValueError(f"forcedPlayoutsK must be a number >= 0 (0 / unset: off), got {forcedPlayoutsK!r}")
+    k = float(k)
+    if not 0.0 <= k < float("inf"):  # (a NaN fails the comparison)
+        raise ValueError(f"forcedPlayoutsK must be finite and >= 0, got {forcedPlayoutsK!r}")
+    prune = True if forcedPrune is None else forcedPrune
+    if not isinstance(prune, (bool, np.bool_)):
+        raise ValueError(f"forcedPrune must be a bool, got {forcedPrune!r}")
+    if k == 0.0 and not prune:
+        raise ValueError("forcedPrune=False needs forcedPlayoutsK > 0: without forced playouts nothing is pruned "
+                         "anyway and the switch would do nothing")
+    return k, bool(prune)
 
 
 def check_ema_knobs(emaDecay=0.0, emaEvery=1):
@@ -510,5 +531,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_playout_knobs", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "augment_examples", "check_playout_knobs", "check_forced_knobs", "policy_prune", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
            "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]
