@@ -399,7 +399,9 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  * 0 edges gathered by the UCB scans (one 16-B edge per visited entry scanned, MCTS.py:122-133; with
  *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env)
  * 1-3 expansions whose prior took the window, the sparse and the general path (their sum: stats 0;
- *   YK_PRIOR_FAST=0 sends every one through the general path)
+ *   YK_PRIOR_FAST=0 sends every one through the general path with the gather P write, =1 keeps the window
+ *   and sparse paths and leaves the general path's P write unstaged; unset or anything else, the general
+ *   path's P write also reads its priors from the window - still counted as general)
  * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena)
  * 5 root picks of the last batch that took a forced edge, 6 visits its pruning took off the recorded counts
  *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena) */

@@ -97,6 +97,13 @@ constexpr int pw_tmax() {
     return t;
 }
 constexpr int PW_GMAX = pw_gmax();  // 8-element groups in the longest leaf
+constexpr int pw_gmin() {
+    const PwPlan p = make_plan();
+    int g = PW_GMAX;
+    for (int i = 0; i < p.nleaf; i++) g = p.len[i] / 8 < g ? p.len[i] / 8 : g;
+    return g;
+}
+constexpr int PW_GMIN = pw_gmin();  // and in the shortest: groups below it need no test
 constexpr int PW_TMAX = pw_tmax() > 0 ? pw_tmax() : 1;  // longest n % 8 tail
 constexpr int pw_lmax() {
     const PwPlan p = make_plan();
@@ -109,6 +116,25 @@ constexpr int pw_lmax() {
 static_assert(NCOMB > pw_lmax(), "two category starts could share a leaf of the pairwise plan");
 static_assert(PF_WCAP % 8 == 0 && PF_WCAP >= 16 && GAMES_PER_BLOCK * PF_WCAP * 4 <= 40 * 1024,
               "the prior window: whole float4 pairs, a slot per category, 16 waves per CU");
+// The staged P write of the general path: the tree's root splits the row where leaf 16
+// starts, lanes 0-31 hold the left half and lanes 32-63 the right; either half fits the window whole
+constexpr int PW_NLEAF = make_plan().nleaf;
+constexpr int PW_SPLIT = make_plan().start[PW_NLEAF / 2];
+static_assert(PW_SPLIT % 8 == 0 && PW_SPLIT <= PF_WCAP && ASIZE - PW_SPLIT <= PF_WCAP,
+              "both halves of the pairwise tree fit the prior window, float4s aligned");
+static_assert(PW_SPLIT > NBID && (PW_SPLIT - NBID) / NCOMB < NCAT, "the split lies inside a category's block");
+constexpr int PW_SPLIT_CAT = (PW_SPLIT - NBID) / NCOMB, PW_SPLIT_COMB = (PW_SPLIT - NBID) % NCOMB;  // 5, 146
+// The second piece starts at the first leaf from which the rest of the row fits the window, below the
+// split: a 10-dice leaf's group of four compact entries that the split cuts (146 = 2 mod 4) stays whole
+constexpr int pw_leaf2() {
+    const PwPlan p = make_plan();
+    int i = 0;
+    while (ASIZE - p.start[i] > PF_WCAP) i++;
+    return i;
+}
+constexpr int PW_LEAF2 = pw_leaf2(), PW_BASE2 = make_plan().start[PW_LEAF2];
+static_assert(PW_LEAF2 <= PW_NLEAF / 2 && PW_BASE2 % 8 == 0 && PW_BASE2 <= PW_SPLIT - (PW_SPLIT_COMB & 3),
+              "the second piece holds the right half and the group the split cuts");
 
 // getValidMoves of player 1 as wave-uniform scalars (the same test as action_valid)
 struct ValidQ {
@@ -964,32 +990,99 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             const float inv_fallback = V > 0 ? 1.0f / (float)V : 0.0f;
             // P over the compact valid set (ascending action): Ps / sum, or the uniform fallback
             // (MCTS.py:90-107).  Written in compact order (coalesced): each prior read back from the
-            // window, or on the general path recomputed exactly as above from the L2-resident logits
-            // row (or the hash).
+            // window, or with YK_PRIOR_FAST=0 / 1 on the general path recomputed exactly as above from the
+            // L2-resident logits row (or the hash).
             const float* __restrict__ xr = d.logits + (long)e * PI_LD;
             // the node summary: the pick of the node's first UCB scan (Ns = 0: every term is
             // u = (c p) sqe0, the scan's own operations and order), from the final p's
             const float sqe0 = (float)sqrt((double)0u + 1e-8);
             float fb = -INFINITY;
             int fj = 0x7FFFFFFF;
-            for (int j0 = lane; j0 < VP; j0 += 256) {  // four gathers in flight per lane
+            // A general leaf's priors are all in q / qt, laid out by action: the window takes them in two
+            // pieces of whole leaves of the pairwise tree (zeros included, so no zero-fill) - the left half
+            // (lanes 0-31, actions below PW_SPLIT), then the leaves from PW_LEAF2 on (actions from
+            // PW_BASE2) - and the loop reads the compact entries [0, jA), then [jA, VP), back from it: no
+            // second gather, no second exp.
+            const bool staged = d.prior_fast >= 2 && !fast && V > 0;
+            // 10 dice: every combination valid, a category's block is NCOMB = 0 mod 4 entries, so the
+            // compact entries j .. j + 3 (j = 0 mod 4) are one category's consecutive actions
+            const bool quad = staged && valid.mode == 0 && valid.n >= 10;
+            // valid actions below the split (the compact order ascends by action); at 10 dice rounded down to
+            // a whole group of four - the second piece's window holds the cut group's actions below the split
+            int jA = 0;
+            if (staged) {
+                if (quad) {  // whole categories of NCOMB, then the cut one's head, down to a whole group
+                    const uint32_t un = ~valid.used & ((1u << NCAT) - 1u);
+                    jA = NCOMB * __builtin_popcount(un & ((1u << PW_SPLIT_CAT) - 1u)) +
+                         (((un >> PW_SPLIT_CAT) & 1u) ? (PW_SPLIT_COMB & ~3) : 0);
+                } else {
+                    int lo = 0, hi = V;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (compact_to_action(vi, mid) < PW_SPLIT) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    jA = __builtin_amdgcn_readfirstlane(lo);
+                }
+            }
+            const int nhalf = staged ? 2 : 1;
+            for (int hf = 0; hf < nhalf; hf++) {
+            const int jlo = hf ? jA : 0, jhi = (staged && !hf) ? jA : VP;
+            if (staged) {
+                wbase = hf ? PW_BASE2 : 0;
+                if (hf) wave_sync();  // the first piece's reads precede the second piece's writes
+                if (hf ? leaf >= PW_LEAF2 : leaf < PW_NLEAF / 2) {
+                    float* wl = win + (st - wbase);
+#pragma unroll
+                    for (int j = 0; j < PW_GMAX; j++)
+                        if (j < PW_GMIN || j < G) *reinterpret_cast<float4*>(wl + 8 * j + 4 * h) = q[j];
+#pragma unroll
+                    for (int r = 0; r < PW_TMAX; r++)
+                        if (h == 0 && r < R) wl[8 * G + r] = qt[r];
+                }
+                wave_sync();
+            }
+            // four entries per lane (jlo, jhi and V = VP are 0 mod 4 here): one action, two 8-byte window
+            // reads (a category starts at 2 mod 4), one 16-byte P and one 8-byte slot store; the same
+            // expressions per entry, ascending j within the lane
+            for (int j = jlo + 4 * lane; quad && j < jhi; j += 256) {
+                const int ci = j / NCOMB;  // (compact_to_action's 10-dice form)
+                const float* w = win + (NBID + NCOMB * (int)((vi.cats >> (4 * ci)) & 0xF) + (j - ci * NCOMB) - wbase);
+                const float2 w01 = *reinterpret_cast<const float2*>(w), w23 = *reinterpret_cast<const float2*>(w + 2);
+                const float pa4[4] = {w01.x, w01.y, w23.x, w23.y};
+                float p4[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const float pa = pa4[u];
+                    const float p = sum > 0.0f ? pa / sum : inv_fallback;
+                    const float u0 = (d.c32 * p) * sqe0;
+                    if (u0 > fb) {
+                        fb = u0;
+                        fj = j + u;
+                    }
+                    p4[u] = p;
+                }
+                *reinterpret_cast<float4*>(P + j) = make_float4(p4[0], p4[1], p4[2], p4[3]);
+                *reinterpret_cast<uint2*>(S + j) = make_uint2(0u, 0u);
+            }
+            for (int j0 = jlo + lane; !quad && j0 < jhi; j0 += 256) {  // four gathers in flight per lane
                 float xa[4];
                 int aa[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int j = j0 + 64 * u;
                     aa[u] = j < V ? compact_to_action(vi, j) : 0;
-                    xa[u] = (d.prior == 0 && !fast && j < V) ? xr[aa[u]] : 0.f;
+                    xa[u] = (d.prior == 0 && !fast && !staged && j < V) ? xr[aa[u]] : 0.f;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int j = j0 + 64 * u;
-                    if (j < VP) {
+                    if (j < jhi) {
                         float p = 0.0f;
                         if (j < V) {
-                            const float pa = fast            ? win[wslot(aa[u])]
-                                             : d.prior == 0 ? softmax_p(xa[u], mx, lse)
-                                                            : hash_prior_pi(hsh, aa[u]);
+                            const float pa = (fast || staged) ? win[wslot(aa[u])]
+                                             : d.prior == 0   ? softmax_p(xa[u], mx, lse)
+                                                              : hash_prior_pi(hsh, aa[u]);
                             p = sum > 0.0f ? pa / sum : inv_fallback;
                             const float u0 = (d.c32 * p) * sqe0;
                             if (u0 > fb) {  // ascending j within the lane: strict '>' keeps the lowest
@@ -1001,6 +1094,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                         S[j] = 0;
                     }
                 }
+            }
             }
             wave_argmax_step(fb, fj);  // the largest u0, the lowest index among equals
             if (lane == 0) {
@@ -1880,10 +1974,11 @@ constexpr int YK_FPARTS_MAX = 4;
         // the same trees; the records' first_j is written either way)
         const char* en = getenv("YK_NODE_SUMMARY");
         d.node_summary = (en && en[0] == '0') ? 0 : 1;
-        // YK_PRIOR_FAST=0: every leaf's prior takes the dense pass (A/B, and the test that both give
-        // the same trees)
+        // YK_PRIOR_FAST=0: every leaf's prior takes the dense pass and the gather P write (A/B, and the
+        // test that all levels give the same trees); 1: the compact-first paths, general leaves unstaged;
+        // unset or anything else: those and the staged P write of the general leaves
         const char* ep = getenv("YK_PRIOR_FAST");
-        d.prior_fast = (ep && ep[0] == '0') ? 0 : 1;
+        d.prior_fast = !ep ? 2 : (ep[0] == '0' && !ep[1]) ? 0 : (ep[0] == '1' && !ep[1]) ? 1 : 2;
         // YK_SPLIT_DESCENT=1 (measurement): k_expand_backup stops after the backup and each next
         // descent is its own k_select launch, so rocprofv3 times and counts the expansion + backup
         // and the descent apart (the same work: the trees are identical)
