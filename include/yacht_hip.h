@@ -378,6 +378,36 @@ int yk_engine_set_forced_playouts(yk_engine_t* eng, double k, int prune);
  * device before any row is read: YK_ERR_RANGE, out untouched.  Synchronises `stream`. */
 int yk_policy_prune(const int64_t* indptr, const int32_t* cols, const int32_t* counts, const double* q, const float* p,
                     const int32_t* ns, int64_t n, double k, double cpuct, int32_t* out, void* stream);
+/* First-play urgency (FPU reduction: Leela, KataGo), a departure from the reference, opt-in; DESIGN.md section
+ * 6g.  Off (on = 0, the state of a new engine): nothing changes.  On, in EVERY search of this engine - yk_selfplay
+ * (full and fast moves), yk_arena (both trees of a dual-tree engine) and yk_mcts_search - at every node with
+ * Ns > 0 that has a visited and an unvisited valid edge.  Doubles and integers unless it says float; c32 =
+ * f32(cpuct), sq = f32(sqrt(Ns)), sqe = f32(sqrt(Ns + 1e-8)):
+ *   visited candidate    the largest u = f32(Q) + ((c32 * P) * sq) / f32(1 + N), the lowest compact index among
+ *                        equals (a forced edge's u is +inf, as without the rule)
+ *   unvisited candidate  the largest x = (c32 * P) * sqe over the unvisited edges, the lowest index among equals
+ *   parent estimate      over the visited edges: W = sum N * llrint(Q * 2^32) (int64, ties to even), Mi = sum
+ *                        (uint64)((double)P * 2^40) (truncated); fq = (float)((W / Ns) / 2^32 - r * sqrt(Mi / 2^40)),
+ *                        r = root_reduction at depth 0 of a search and `reduction` elsewhere
+ *   winner               the larger of the visited u and fq + x (one f32 add), the lower index on equality
+ * A node at Ns = 0 and a node whose valid edges are all visited are scanned as without the rule.  The parent
+ * estimate is the children's visit-weighted mean, not the node's own net value (the node record has no room
+ * for one).  reduction = 0 is legal and is not off.  Lives in the engine, not in yk_engine_config_t.
+ * NULL engine, or a reduction that is negative, NaN or infinite: YK_ERR_ARG, the engine unchanged.  Touches no
+ * device memory. */
+int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_reduction);
+/* The rule's pick alone, on n nodes given as a CSR: DEVICE indptr[n + 1], and per entry p (P, float), counts
+ * (N; an entry with N <= 0 is an unvisited edge), q (Q, read where N > 0); per row ns[n] (Ns, negative taken as
+ * 0) -> DEVICE pick[n], the picked entry's index within its row (-1: an empty row), and unvisited[n], 1 when
+ * that entry is an unvisited edge.  A row at Ns = 0, or with one kind of edge only, takes the plain argmax
+ * over u and x (the lowest index among equals).  The same device functions as the search kernels; one
+ * wavefront per row; no atomics on data; equal inputs give equal bits.  A NULL pointer, n < 0, a reduction
+ * negative, NaN or infinite, a cpuct that is not finite, or outputs that alias counts, ns or each other:
+ * YK_ERR_ARG before anything touches the device.  An indptr that starts below 0 or decreases (or a row of more
+ * than 2^31 - 1 entries), detected on the device before any row is read: YK_ERR_RANGE, the outputs untouched.
+ * Synchronises `stream`. */
+int yk_fpu_pick(const int64_t* indptr, const float* p, const int32_t* counts, const double* q, const int32_t* ns,
+                int64_t n, double cpuct, double reduction, int32_t* pick, int32_t* unvisited, void* stream);
 /* Per-kernel timing with HIP events on the engine's stream; resets the accumulators.
  * enable = 0 off, k > 0 on: the per-move launches are timed every time, the per-simulation
  * forward / expand pair in every k-th simulation of a move (1 = all; an event record between
@@ -404,7 +434,9 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  *   path's P write also reads its priors from the window - still counted as general)
  * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena)
  * 5 root picks of the last batch that took a forced edge, 6 visits its pruning took off the recorded counts
- *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena) */
+ *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena)
+ * 7 descent picks of the last batch (every depth) that first-play urgency gave to the unvisited candidate,
+ *   8 picks its rule decided: nodes with both kinds of edge (yk_engine_set_fpu; both 0 with it off) */
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)

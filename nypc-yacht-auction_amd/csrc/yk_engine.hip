@@ -26,6 +26,7 @@
 #include "yk_common.h"
 #include "yk_engine_dev.h"
 #include "yk_forced.h"
+#include "yk_fpu.h"
 #include "yk_net.h"
 
 #define YK_MAX_GROUPS 8
@@ -367,11 +368,15 @@ __global__ __launch_bounds__(256) void k_move_begin(EngDev d, int move, int exte
 // FORCED (a full self-play move with forced playouts): a visited edge that forced_edge names
 // has u = +inf - only the visited list changes, an unvisited edge is never forced - and `fpick` is set when
 // such an edge is the winner.
-template <bool FORCED>
+// FPU (first-play urgency): the visited list's loop also adds the two integer sums of the parent
+// estimate, the walk is the same (x = (c P) sqe is monotone in P, so the band logic holds), and the last
+// comparison is yk_fpu.h's: the visited list's winner against fq + ub.  `fcnt` gets 1 (the rule decided: the
+// root has both kinds of edge) | 2 (the unvisited candidate won).
+template <bool FORCED, bool FPU>
 __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint32_t nv, const float* P,
                                          const uint16_t* S, const Edge* edges, int V, int nk, int ws, float sq,
                                          float sqe, uint32_t& wtag, uint64_t& scanned, uint64_t& gathered,
-                                         uint32_t Ns, double fk, int& fpick) {
+                                         uint32_t Ns, double fk, int& fpick, double fr, int& fcnt) {
     const uint16_t* oj = d.ro_j + (long)t * RO_K;
     const float* op = d.ro_p + (long)t * RO_K;
     const uint32_t* rv = d.rv + (long)t * RV_CAP;
@@ -382,6 +387,8 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
     float best = -INFINITY;
     int bj = 0x7FFFFFFF;
     uint32_t btag = 0;
+    int64_t fw = 0;   // FPU: this lane's part of W and of Mi
+    uint64_t fm = 0;
     for (uint32_t i = (uint32_t)lane; i < nv; i += 64) {
         const uint32_t w = rv[i];
         const int j = (int)(w & 0xFFFu);
@@ -389,6 +396,10 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
         const Edge ev = edges[(w >> 12) - 1];
         float u = (float)ev.Q + ((d.c32 * p) * sq) / (float)(ev.N + 1);
         if (FORCED && forced_edge(ev.N, p, Ns, fk)) u = INFINITY;
+        if (FPU) {
+            fw += fpu_w_term(ev.N, ev.Q);
+            fm += fpu_m_term(p);
+        }
         if (u > best || (u == best && j < bj)) {
             best = u;
             bj = j;
@@ -436,6 +447,31 @@ __device__ __forceinline__ int root_scan(const EngDev& d, int t, int lane, uint3
         gathered += (uint64_t)nv;                     // (one edge per visited-list entry)
         return -1;
     }
+    if (FPU) {  // the visited list's winner first, then yk_fpu.h's comparison (every lane holds every term)
+        const int mine = bj;
+        wave_argmax_step(best, bj);
+        const uint64_t own = __ballot(mine == bj);
+        wtag = own ? __builtin_amdgcn_readlane(btag, (int)__builtin_ctzll(own)) : 0u;
+        const bool vis = bj != 0x7FFFFFFF;
+        if (found && vis) {
+            const float fq = fpu_value((int64_t)fpu_wave_sum((uint64_t)fw), fpu_wave_sum(fm), Ns, fr);
+            fcnt = 1;
+            if (fpu_unvisited_wins(fq, ub, uj, best, bj)) {
+                fcnt = 3;
+                best = ub;  // (finite: not a forced pick)
+                bj = uj;
+                wtag = 0u;
+            }
+        } else if (found) {
+            best = ub;
+            bj = uj;
+            wtag = 0u;
+        }
+        if (FORCED) fpick = best == INFINITY;
+        scanned += (uint64_t)nv + (uint64_t)walked;
+        gathered += (uint64_t)nv;
+        return bj;
+    }
     if (lane == 0 && found && (ub > best || (ub == best && uj < bj))) {
         best = ub;
         bj = uj;
@@ -479,12 +515,22 @@ __device__ __forceinline__ void select_none(const EngDev& d, int e, int lane) {
 // root (root_c: set after a lookup that followed the test) or a cached child (an edge tag: the backup
 // caches only ids of records, the next level's node, the new leaf or a node without valid actions;
 // after a terminal break end_id is 0 and nothing is cached) - needs no Es test and no lookup.
-template <bool FORCED>
+//
+// FPU: first-play urgency (the arithmetic of yk_fpu.h) at every node with Ns > 0 that has both a
+// visited and an unvisited edge, on every path: root_scan, and the full scan, which then keeps two running bests
+// (the visited u, the unvisited x) and the two integer sums per lane.  A node at Ns = 0 (the summary's, or a
+// full scan over unvisited edges only) and a node whose edges are all visited come out as before.
+template <bool FORCED, bool FPU>
 __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, int t, int g, const uint32_t* env_ids,
-                                            uint64_t* ctr_arr, const ForcedDev& fd) {
+                                            uint64_t* ctr_arr, const ForcedDev& fd, const FpuDev& fp) {
     // FORCED: 1 when the root's pick was a forced edge.  (Declared first: among the locals below it reorders two
     // phi nodes of the default instantiation, and the register allocation with them.)
     int fpick = 0;
+    // FPU: root_scan's report (1: the rule decided | 2: the unvisited candidate won), then the descent's picks the
+    // rule decided and those of them the unvisited candidate won.  (Declared here for the same reason: as a local
+    // of the root's block, fcnt rotates four phi nodes of the default instantiation.)
+    int fcnt = 0;
+    int fpu_n = 0, fpu_u = 0;
     YkS s = ld_state(d.root + e);
     Stream rs{d.seed, env_ids[e], ctr_arr[e]};
     const NodeRec* nodes = d.nodes[g] + (long)t * d.NCAP;
@@ -525,12 +571,17 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
         }
         if (rid != 0 && uni(rc1.z) != RV_OFF) {  // k_root_sort ran this move: root_c holds the root
             const float sq = (float)sqrt((double)f.Ns), sqe = (float)sqrt((double)f.Ns + 1e-8);
-            pre_bj = __builtin_amdgcn_readfirstlane(root_scan<FORCED>(d, t, lane, rc1.z, Pbase + rc.y, Sbase + rc.y, edges,
-                                                                      (int)rc.z, (int)rc.w, (int)rc1.w, sq, sqe, pre_tag,
-                                                                      scanned, gathered, f.Ns, fd.k, fpick));
+            pre_bj = __builtin_amdgcn_readfirstlane(root_scan<FORCED, FPU>(
+                d, t, lane, rc1.z, Pbase + rc.y, Sbase + rc.y, edges, (int)rc.z, (int)rc.w, (int)rc1.w, sq, sqe, pre_tag,
+                scanned, gathered, f.Ns, fd.k, fpick, fp.r_root, fcnt));
             pre_tag = __builtin_amdgcn_readfirstlane(pre_tag);
             pre = pre_bj != -1;
             if (FORCED) fpick = pre ? __builtin_amdgcn_readfirstlane(fpick) : 0;
+            if (FPU && pre) {
+                fcnt = __builtin_amdgcn_readfirstlane(fcnt);
+                fpu_n += fcnt & 1;
+                fpu_u += fcnt >> 1;
+            }
         }
     }
     while (true) {
@@ -582,6 +633,11 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
             float best = -INFINITY;
             int bj = 0x7FFFFFFF;
             uint32_t btag = 0;  // the edge tag of the lane's best entry (0: unvisited)
+            // FPU: `best` / `bj` / `btag` are the visited candidate's, these the unvisited one's and the sums
+            float bestx = -INFINITY;
+            int bjx = 0x7FFFFFFF;
+            int64_t fw = 0;
+            uint64_t fm = 0;
             // the node summary (an interior node, or a root in full-scan mode): at Ns = 0 no edge is
             // visited and every term is (c P) sqe0, so the pick is the one the expansion stored.  It
             // seeds every lane and leaves the scan nothing to read (a second exit path here spills).
@@ -624,7 +680,20 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
                         } else {
                             u = cp * sqe;
                         }
-                        if (u > best) {
+                        if (FPU) {
+                            if (sv[t]) {
+                                fw += fpu_w_term(ev[t].N, ev[t].Q);
+                                fm += fpu_m_term(pv[t]);
+                                if (u > best) {
+                                    best = u;
+                                    bj = j;
+                                    btag = ev[t].tag;
+                                }
+                            } else if (u > bestx) {
+                                bestx = u;
+                                bjx = j;
+                            }
+                        } else if (u > best) {
                             best = u;
                             bj = j;
                             btag = sv[t] ? ev[t].tag : 0u;
@@ -633,6 +702,24 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
                 }
             }
             if (Vs) wave_argmax_step(best, bj);  // (a stored pick: every lane holds it)
+            if (FPU && Vs) {
+                wave_argmax_step(bestx, bjx);
+                const bool vis = bj != 0x7FFFFFFF, unv = bjx != 0x7FFFFFFF;
+                bool unv_won = unv;  // (no visited edge: the unvisited candidate, as without the rule)
+                if (vis && unv) {    // (Ns > 0: a visited edge was backed up through this node)
+                    const float fq = fpu_value((int64_t)fpu_wave_sum((uint64_t)fw), fpu_wave_sum(fm), Ns, depth == 0 ? fp.r_root : fp.r);
+                    unv_won = fpu_unvisited_wins(fq, bestx, bjx, best, bj);
+                    fpu_n++;
+                    fpu_u += unv_won;
+                }
+                // the unvisited candidate as the wave's best on every lane: finite (not a forced pick), tag 0.
+                // What follows is then the code of the default instantiation, statement for statement
+                if (unv_won) {
+                    best = bestx;
+                    bj = bjx;
+                    btag = 0u;
+                }
+            }
             if (FORCED && depth == 0) fpick = best == INFINITY;
             scanned += (uint64_t)Vs;
             bj_out = bj;
@@ -689,6 +776,10 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
         atomicAdd(gs + 2, (unsigned long long)depth);
         atomicAdd(gs + 7, 1ull);
         if (FORCED) atomicAdd(gs + 12, (unsigned long long)fpick);
+        if (FPU) {
+            atomicAdd(gs + 14, (unsigned long long)fpu_u);
+            atomicAdd(gs + 15, (unsigned long long)fpu_n);
+        }
         atomicAdd(gs + 8, (unsigned long long)gathered);
     }
 }
@@ -698,9 +789,16 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
 // feature (one more argument, even unread, changes the register allocation).
 __device__ __forceinline__ ForcedDev forced_arg() { return ForcedDev{0.0, 0.0}; }
 __device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd) { return fd; }
-template <bool FORCED, class... FD>
+// and FpuDev, after it, for the FPU instantiations: the pack is (), (ForcedDev), (FpuDev) or both
+__device__ __forceinline__ ForcedDev forced_arg(const FpuDev&) { return ForcedDev{0.0, 0.0}; }
+__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd, const FpuDev&) { return fd; }
+__device__ __forceinline__ FpuDev fpu_arg() { return FpuDev{0.0, 0.0}; }
+__device__ __forceinline__ FpuDev fpu_arg(const ForcedDev&) { return FpuDev{0.0, 0.0}; }
+__device__ __forceinline__ const FpuDev& fpu_arg(const FpuDev& fp) { return fp; }
+__device__ __forceinline__ const FpuDev& fpu_arg(const ForcedDev&, const FpuDev& fp) { return fp; }
+template <bool FORCED, bool FPU, class... FD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(sizeof...(FD) == (FORCED ? 1 : 0), "ForcedDev with FORCED, else no further argument");
+    static_assert(sizeof...(FD) == (FORCED ? 1 : 0) + (FPU ? 1 : 0), "ForcedDev with FORCED, FpuDev with FPU, no further argument");
     const int lane = threadIdx.x & 63;
     // the wave's game as a scalar: every per-game base address is then scalar arithmetic, which keeps
     // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
@@ -712,17 +810,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
     const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
-    select_game<FORCED>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...));
+    select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...), fpu_arg(fd...));
 }
 
 // Leaf expansion (MCTS.py:84-115) and backup (MCTS.py:154-164) of this simulation, then -
 // when do_select - the next simulation's descent for the same game (one kernel boundary per
 // simulation fewer).  One wave per game.
 __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane, int t, int g);
-template <bool FORCED, class... FD>  // (FD: as k_select)
+template <bool FORCED, bool FPU, class... FD>  // (FD: as k_select)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
     EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(sizeof...(FD) == (FORCED ? 1 : 0), "ForcedDev with FORCED, else no further argument");
+    static_assert(sizeof...(FD) == (FORCED ? 1 : 0) + (FPU ? 1 : 0), "ForcedDev with FORCED, FpuDev with FPU, no further argument");
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
@@ -738,7 +836,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_W
             return;
         }
         wave_sync();  // this wave's backup writes (edges, slots, Ns) precede its descent's reads
-        select_game<FORCED>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...));
+        select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...), fpu_arg(fd...));
     }
 }
 
@@ -1632,6 +1730,8 @@ struct yk_engine {
     int64_t fast_moves = 0;      // lock-step moves of the last batch that ran with the fast cap
     double forced_k = 0.0;       // forced playouts (yk_engine_set_forced_playouts; 0: off) at the self-play roots
     bool forced_prune = true;    // of full moves, and whether k_move_end prunes the move's counts
+    bool fpu_on = false;         // first-play urgency (yk_engine_set_fpu) in every search of this
+    double fpu_r = 0.0, fpu_r_root = 0.0;  // engine: the reduction at interior nodes and at depth 0
     yk_engine() = default;
     yk_engine(const yk_engine&) = delete;
     yk_engine& operator=(const yk_engine&) = delete;
@@ -1724,23 +1824,36 @@ int check_errors(yk_engine* eng, hipStream_t s) {
 // before the first descent, phase 1 after simulation 0's expansion, which then ends without the
 // fused descent whatever the root-scan mode.  -1: no noise launch is made.
 // forced (a full self-play move with forced playouts): the descents are the FORCED
-// instantiations; every other caller runs the default ones, whose code the feature leaves as it was.
+// instantiations; every other caller runs the unforced ones, whose code the feature leaves as it was.
+// Whether they are the FPU ones is the engine's state (yk_engine_set_fpu), the same for every caller.
 int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint32_t* env_ids, uint64_t* ctr,
              int noise_move = -1, const ForcedDev* forced = nullptr) {
     const dim3 bb(256);
     if (sims <= 0) return YK_OK;
+    // first-play urgency: every search of an engine it is set on runs the FPU instantiations
+    const bool fpu = eng->fpu_on;
+    const FpuDev fp{eng->fpu_r, eng->fpu_r_root};
     const auto select = [&](const EngDev& dd, hipStream_t s) {
-        if (forced)
-            hipLaunchKernelGGL((k_select<true, ForcedDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced);
+        if (forced && fpu)
+            hipLaunchKernelGGL((k_select<true, true, ForcedDev, FpuDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced, fp);
+        else if (forced)
+            hipLaunchKernelGGL((k_select<true, false, ForcedDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced);
+        else if (fpu)
+            hipLaunchKernelGGL((k_select<false, true, FpuDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, fp);
         else
-            hipLaunchKernelGGL((k_select<false>), game_grid(dd), bb, 0, s, dd, env_ids, ctr);
+            hipLaunchKernelGGL((k_select<false, false>), game_grid(dd), bb, 0, s, dd, env_ids, ctr);
     };
     const auto expand_backup = [&](const EngDev& dd, hipStream_t s, int do_select) {
-        if (forced)
-            hipLaunchKernelGGL((k_expand_backup<true, ForcedDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr,
+        if (forced && fpu)
+            hipLaunchKernelGGL((k_expand_backup<true, true, ForcedDev, FpuDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids,
+                               ctr, *forced, fp);
+        else if (forced)
+            hipLaunchKernelGGL((k_expand_backup<true, false, ForcedDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr,
                                *forced);
+        else if (fpu)
+            hipLaunchKernelGGL((k_expand_backup<false, true, FpuDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr, fp);
         else
-            hipLaunchKernelGGL((k_expand_backup<false>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr);
+            hipLaunchKernelGGL((k_expand_backup<false, false>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr);
     };
     EngDev dg[YK_MAX_GROUPS];
     for (int g = 0; g < G; g++) {
@@ -2145,6 +2258,15 @@ int yk_engine_set_forced_playouts(yk_engine_t* eng, double k, int prune) {
     return YK_OK;
 }
 
+int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_reduction) {
+    if (!eng || !(reduction >= 0.0) || std::isinf(reduction) || !(root_reduction >= 0.0) || std::isinf(root_reduction))
+        return YK_ERR_ARG;  // (a NaN fails >= 0)
+    eng->fpu_on = on != 0;
+    eng->fpu_r = reduction;
+    eng->fpu_r_root = root_reduction;
+    return YK_OK;
+}
+
 int yk_playout_schedule(uint64_t seed, uint32_t env_base, double full_prob, int n_moves, uint8_t* full) {
     if (!full || n_moves < 0 || !(full_prob >= 0.0 && full_prob <= 1.0)) return YK_ERR_ARG;
     for (int m = 0; m < n_moves; m++) full[m] = playout_full(seed, env_base, m, full_prob) ? 1 : 0;
@@ -2274,14 +2396,15 @@ int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n) {
     YK_HIP(hipDeviceSynchronize());
     YK_HIP(hipMemcpy(gs.data(), d.gstats, sizeof(uint64_t) * gs.size(), hipMemcpyDeviceToHost));
     // scan edges; expansions by prior path: window, sparse, general; the playout cap's fast moves; root picks
-    // that took a forced edge and visits the pruning took off the recorded counts
-    int64_t c[7] = {0, 0, 0, 0, eng->fast_moves, 0, 0};
+    // that took a forced edge and visits the pruning took off the recorded counts; descent picks
+    // first-play urgency gave to the unvisited candidate, and picks its rule decided
+    int64_t c[9] = {0, 0, 0, 0, eng->fast_moves, 0, 0, 0, 0};
     for (int e = 0; e < d.E; e++) {
         c[0] += (int64_t)gs[(size_t)e * GST + 8];
         for (int k = 0; k < 3; k++) c[1 + k] += (int64_t)gs[(size_t)e * GST + 9 + k];
-        for (int k = 0; k < 2; k++) c[5 + k] += (int64_t)gs[(size_t)e * GST + 12 + k];
+        for (int k = 0; k < 4; k++) c[5 + k] += (int64_t)gs[(size_t)e * GST + 12 + k];
     }
-    for (int i = 0; i < n; i++) out[i] = i < 7 ? c[i] : 0;
+    for (int i = 0; i < n; i++) out[i] = i < 9 ? c[i] : 0;
     return YK_OK;
 }
 

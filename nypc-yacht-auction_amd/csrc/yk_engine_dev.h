@@ -138,7 +138,8 @@ struct EngDev {
     yk_state_t* rec_leaf;  // [R][max_exp] the expanded leaf (canonical state)
     // stats
     uint64_t* gstats;      // [E][GST]: expansions, scanned, path edges, vnew, max nodes, max edges, max arena, sims,
-                           // edge gathers of the UCB scans, expansions by prior path (window, sparse, general)
+                           // edge gathers of the UCB scans, expansions by prior path (window, sparse, general),
+                           // forced root picks, pruned visits (s6f), first-play urgency's unvisited picks and picks (s6g)
     uint32_t* err;         // [1] error bits
 };
 

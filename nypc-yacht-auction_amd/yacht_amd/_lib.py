@@ -135,6 +135,8 @@ SIGNATURES = {
     "yk_policies_take": [P, P, P, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, P],
     "yk_engine_set_forced_playouts": [P, C.c_double, I],
     "yk_policy_prune": [P, P, P, P, P, P, C.c_int64, C.c_double, C.c_double, P, P],
+    "yk_engine_set_fpu": [P, I, C.c_double, C.c_double],
+    "yk_fpu_pick": [P, P, P, P, P, C.c_int64, C.c_double, C.c_double, P, P, P],
     "yk_ema_weight": [C.c_double, C.c_int64, P],
     "yk_ema_update": [P, P, C.c_int64, C.c_float, P],
     "yk_trainer_set_ema": [P, C.c_double, I],
@@ -148,7 +150,7 @@ _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_re
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
 # search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap, the
-# averaged weights and the forced playouts (A/B baselines may predate them)
+# averaged weights, the forced playouts and the first-play urgency (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
@@ -156,7 +158,7 @@ _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk
           "yk_engine_root_prior", "yk_engine_set_playout_cap", "yk_playout_schedule", "yk_examples_full_rows",
           "yk_policies_take", "yk_ema_weight", "yk_ema_update", "yk_trainer_set_ema", "yk_trainer_ema_buffer",
           "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state", "yk_engine_set_forced_playouts",
-          "yk_policy_prune"}
+          "yk_policy_prune", "yk_engine_set_fpu", "yk_fpu_pick"}
 _lib = None
 
 

@@ -22,6 +22,9 @@ any number of ranks (one process per GPU, torch.distributed):
   reference): at the roots of self-play's full moves a visited child is searched until
   N^2 >= k P Ns, and the forced visits the search's PUCT values did not justify are taken off the recorded
   counts, which the policy targets are made of.
+* first-play urgency (opt-in, ``args.fpuReduction``, ``fpuRootReduction``; not in the reference):
+  an unvisited edge starts from the visited children's visit-weighted mean less a reduction, not from 0 - in
+  everything that searches: self-play, the held-out games, the reanalysis, the gate, ``MCTSArena``, the plugin.
 * held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
   iteration that never enter training, on which the previous and the new net are evaluated after
   train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
@@ -104,12 +107,16 @@ class Coach:
         from .replay import check_forced_knobs
         self.forced_k, self.forced_prune = check_forced_knobs(args.get("forcedPlayoutsK", None),
                                                               args.get("forcedPrune", None))
+        # first-play urgency in every search made for this Coach.  Unset: off
+        from .replay import check_fpu_knobs
+        self.fpu_reduction, self.fpu_root_reduction = check_fpu_knobs(args.get("fpuReduction", None),
+                                                                      args.get("fpuRootReduction", None))
         # averaged weights: NNetWrapper's knobs, checked here as well.  With emaDecay set the
         # net that plays, gates and reanalyses is the averaged one (NNetWrapper.yk_net); learn's flow is unchanged
         from .replay import check_ema_knobs
         self.ema_decay, self.ema_every = check_ema_knobs(args.get("emaDecay", 0.0), args.get("emaEvery", 1))
         # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims); with forcedPlayoutsK also
-        # {"forced_picks", "pruned_visits"} (this rank's)
+        # {"forced_picks", "pruned_visits"} and with fpuReduction {"fpu_unvisited_picks", "fpu_picks"} (this rank's)
         self.last_selfplay = None
         self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
@@ -148,7 +155,9 @@ class Coach:
                               # the playout cap; the held-out games are played under the same config
                               playout_fast_sims=self.playout_fast_sims, playout_full_prob=self.playout_full_prob,
                               # forced playouts and pruning; again the same for the held-out games
-                              forced_playouts_k=self.forced_k, forced_prune=self.forced_prune)
+                              forced_playouts_k=self.forced_k, forced_prune=self.forced_prune,
+                              # first-play urgency; the same for the held-out games
+                              fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction)
 
     def _value_targets_on(self) -> bool:
         return (self.value_mix, self.value_lambda) != (0.0, 1.0)
@@ -190,6 +199,9 @@ class Coach:
         if self.forced_k > 0:
             self.last_selfplay.update(forced_picks=st["forced_picks"], pruned_visits=st["pruned_visits"])
             forced = ", %d forced root picks, %d visits pruned" % (st["forced_picks"], st["pruned_visits"])
+        if self.fpu_reduction is not None:
+            self.last_selfplay.update(fpu_unvisited_picks=st["fpu_unvisited_picks"], fpu_picks=st["fpu_picks"])
+            forced += ", %d of %d first-play-urgency picks unvisited" % (st["fpu_unvisited_picks"], st["fpu_picks"])
         log.info("SELF-PLAY %d moves searched, %d examples kept, %d lock-step sims run (this rank)%s"
                  % (shard.n_searched, len(shard), sims_run, forced))
         return shard
@@ -218,7 +230,8 @@ class Coach:
                 m = int(idx.numel())
                 if m:
                     H[j] = reanalyse(item, idx, net=net, prior=prior, sims=self.reanalyse_sims,
-                                     cpuct=self.args.cpuct, seed=self.game.rng.seed, env_base=self._streams(m))
+                                     cpuct=self.args.cpuct, seed=self.game.rng.seed, env_base=self._streams(m),
+                                     fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction)
                     report.append(dict(item=j, n=n, reanalysed=m, n_empty=H[j].reanalysis["n_empty"]))
             base += n
         self.last_reanalysis = report

@@ -24,7 +24,8 @@ class SelfPlayEngine:
                  max_expansions: int = 0, arena_entries: int = 0, record_stride: int = 1, groups: int = 0,
                  dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
                  dirichlet_eps: float = 0.0, record_root_values: bool = False, playout_fast_sims: int = 0,
-                 playout_full_prob: float = 1.0, forced_playouts_k: float = 0.0, forced_prune: bool = True):
+                 playout_full_prob: float = 1.0, forced_playouts_k: float = 0.0, forced_prune: bool = True,
+                 fpu_reduction=None, fpu_root_reduction=None):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -62,6 +63,22 @@ class SelfPlayEngine:
         if self.forced_playouts_k != 0.0:
             try:
                 call("yk_engine_set_forced_playouts", self.handle, self.forced_playouts_k, int(self.forced_prune))
+            except Exception:
+                self.close()
+                raise
+        # first-play urgency in every search of this engine - run(), arena() (both trees) and yk_mcts_search
+        # (DESIGN.md 6g): an unvisited edge starts from the visited children's visit-weighted mean less
+        # fpu_reduction * sqrt(prior mass tried) - fpu_root_reduction at depth 0, by default the same - instead
+        # of from 0.  None is off; 0 is legal and is not off
+        if fpu_reduction is None and fpu_root_reduction is not None:
+            self.close()
+            raise ValueError("fpu_root_reduction needs fpu_reduction: alone it would silently do nothing")
+        self.fpu_reduction = None if fpu_reduction is None else float(fpu_reduction)
+        self.fpu_root_reduction = (self.fpu_reduction if fpu_root_reduction is None or fpu_reduction is None
+                                   else float(fpu_root_reduction))
+        if self.fpu_reduction is not None:
+            try:
+                call("yk_engine_set_fpu", self.handle, 1, self.fpu_reduction, self.fpu_root_reduction)
             except Exception:
                 self.close()
                 raise
@@ -137,8 +154,10 @@ class SelfPlayEngine:
     # fast_moves: the lock-step moves of the last batch that ran with the fast playout cap
     # forced_picks / pruned_visits: the last batch's root picks that took a forced edge, and the visits the
     # pruning took off its recorded counts
+    # fpu_unvisited_picks / fpu_picks: the last batch's descent picks (every depth) that first-play urgency gave
+    # to the unvisited candidate, and the picks its rule decided - nodes with both kinds of edge
     COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general", "fast_moves", "forced_picks",
-                     "pruned_visits")
+                     "pruned_visits", "fpu_unvisited_picks", "fpu_picks")
 
     def stats(self) -> dict:
         out = np.zeros(16, dtype=np.int64)

@@ -449,11 +449,41 @@ def policy_prune(indptr, cols, counts, q, p, ns, k: float, cpuct: float, stream=
     return out
 
 
+# ---------------------------------------------------------------- first-play urgency
+def fpu_pick(indptr, p, counts, q, ns, cpuct: float, reduction: float, stream=None):
+    """The UCB pick under first-play urgency of nodes given as a CSR (yk_fpu_pick), the rule of the search
+    kernels' FPU instantiations: device tensors indptr int64 [n + 1], and per entry p float32 (P), counts int32
+    (N; 0: an unvisited edge), q float64 (Q); ns int32 [n] (each node's visit count); cpuct the search's and
+    reduction the rule's r.  Returns (pick, unvisited), device int32 [n]: the picked entry's index within its
+    row (-1: an empty row) and 1 where that entry is an unvisited edge.  ValueError for row pointers that start
+    below 0 or decrease.  Synchronises."""
+    want = ((indptr, torch.int64), (p, torch.float32), (counts, torch.int32), (q, torch.float64), (ns, torch.int32))
+    for t, dt in want:
+        if t.dtype != dt or t.dim() != 1:
+            raise TypeError("fpu_pick takes vectors: indptr int64, p float32, counts / ns int32, q float64")
+    n = int(indptr.numel()) - 1
+    if n < 0 or int(ns.numel()) != n or not (p.numel() == counts.numel() == q.numel()):
+        raise ValueError("fpu_pick: indptr has n + 1 entries, ns n, and p / counts / q one per edge")
+    pick = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    unv = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    # (an empty CSR's tensors may have no storage: any non-null pointer does, nothing is read or written there)
+    spare = torch.empty(2, dtype=torch.int64, device="cuda")
+    a = [ptr(t) or ptr(spare) for t in (p, counts, q, ns)]
+    try:
+        call("yk_fpu_pick", ptr(indptr), a[0], a[1], a[2], a[3], n, float(cpuct), float(reduction), ptr(pick), ptr(unv),
+             stream_ptr(stream))
+    except _lib.YkError as err:
+        if err.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError("fpu_pick: indptr must start at >= 0 and never decrease") from None
+    return pick[:n], unv[:n]
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
            "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice",
-           "examples_full_rows", "policies_take", "policy_prune", "_lib"]
+           "examples_full_rows", "policies_take", "policy_prune", "fpu_pick", "_lib"]
 
 
 def greedy_action(states):

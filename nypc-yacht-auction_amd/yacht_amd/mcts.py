@@ -23,11 +23,14 @@ class MCTS:
 
     def _eng(self):
         if self._engine is None:
+            from .replay import fpu_knobs_of
+            fpu = fpu_knobs_of(self.args)  # first-play urgency (args.fpuReduction); unset: off
             if getattr(self.nnet, "yk_prior", None) == "hash":
-                self._engine = SelfPlayEngine(1, self.args.numMCTSSims, self.args.cpuct, prior="hash", max_moves=1)
+                self._engine = SelfPlayEngine(1, self.args.numMCTSSims, self.args.cpuct, prior="hash", max_moves=1,
+                                              **fpu)
             else:
                 self._engine = SelfPlayEngine(1, self.args.numMCTSSims, self.args.cpuct, net=self.nnet.yk_net(),
-                                              max_moves=1)
+                                              max_moves=1, **fpu)
             call("yk_mcts_reset", self._engine.handle)
         return self._engine
 

@@ -13,6 +13,7 @@ iterates the reference's tuples, and for training on them (``policy_target="visi
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import deque
 
 import numpy as np
@@ -166,6 +167,37 @@ def check_forced_knobs(forcedPlayoutsK=None, forcedPrune=None):
         raise ValueError("forcedPrune=False needs forcedPlayoutsK > 0: without forced playouts nothing is pruned "
                          "anyway and the switch would do nothing")
     return k, bool(prune)
+
+
+def check_fpu_knobs(fpuReduction=None, fpuRootReduction=None):
+    """(reduction, root_reduction) of the first-play urgency as (float or None, float or None):
+    fpuReduction unset is off - (None, None) - else a finite number >= 0 (0 is legal and is not off: unvisited
+    edges then start at the parent's estimate); fpuRootReduction (default: fpuReduction) is the reduction at
+    depth 0 of a search.  ValueError for anything else, and for fpuRootReduction without fpuReduction (it
+    would silently do nothing)."""
+    def number(name, x):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number >= 0 (unset: off), got {x!r}")
+        x = float(x)
+        if not (x >= 0.0) or math.isinf(x):
+            raise ValueError(f"{name} must be finite and >= 0, got {x!r}")
+        return x
+    if fpuReduction is None:
+        if fpuRootReduction is not None:
+            raise ValueError("fpuRootReduction needs fpuReduction: without it first-play urgency is off and the "
+                             "root reduction would silently do nothing")
+        return None, None
+    r = number("fpuReduction", fpuReduction)
+    return r, (r if fpuRootReduction is None else number("fpuRootReduction", fpuRootReduction))
+
+
+def fpu_knobs_of(args) -> dict:
+    """args.fpuReduction / args.fpuRootReduction, checked, as SelfPlayEngine's keyword arguments - what everything
+    that searches for a Coach passes to its engine, so a net trained on FPU searches is gated and played under
+    them as well."""
+    get = args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+    r, rr = check_fpu_knobs(get("fpuReduction", None), get("fpuRootReduction", None))
+    return dict(fpu_reduction=r, fpu_root_reduction=rr)
 
 
 def check_ema_knobs(emaDecay=0.0, emaEvery=1):
@@ -325,7 +357,8 @@ def check_reanalyse_knobs(reanalyseFraction=0.0, reanalyseSims=None, numMCTSSims
 
 
 def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: int, cpuct: float, seed: int,
-              env_base: int = 0, chunk: int = 4096, env_ids=None, ctr=None) -> ExampleShard:
+              env_base: int = 0, chunk: int = 4096, env_ids=None, ctr=None, fpu_reduction=None,
+              fpu_root_reduction=None) -> ExampleShard:
     """Examples idx of a shard searched again (MuZero's reanalyse): their boards are the roots
     of `sims` simulations of yk_mcts_search on fresh trees with `net` (a YkNet, or a wrapper with yk_net();
     prior="hash": the test prior), and their policy rows and targets become the new search's.
@@ -335,7 +368,8 @@ def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: i
     Root j draws from the game stream (seed, env_base + j) from counter 0 - or from env_ids[j] / ctr[j] where
     given.  The last, partial chunk is padded with copies of its first root on the stream ids after the
     call's last one; their searches are dropped (they consume nothing: a stream is a function of its id).
-    No root noise is ever added.
+    No root noise is ever added.  fpu_reduction / fpu_root_reduction: the searches run under first-play urgency
+    (SelfPlayEngine's knobs; None: off).
 
     A reanalysed row holds the visit distribution N / sum N of its new search and its target the most visited
     action (the lowest on ties) - also where the stored row was the one-hot of a temp-0 move, so afterwards
@@ -394,7 +428,8 @@ def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: i
         c0[:m] = c_in
     sp = stream_ptr()
     counts = torch.empty((E, K.ACTION_SIZE), dtype=torch.int32, device="cuda")
-    eng = SelfPlayEngine(E, int(sims), float(cpuct), net=net, prior=prior, max_moves=1)
+    eng = SelfPlayEngine(E, int(sims), float(cpuct), net=net, prior=prior, max_moves=1, fpu_reduction=fpu_reduction,
+                         fpu_root_reduction=fpu_root_reduction)
     parts, tparts, n_empty, chunks = [], [], 0, 0
     try:
         for j0 in range(0, m, E):
@@ -531,5 +566,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_playout_knobs", "check_forced_knobs", "policy_prune", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "augment_examples", "check_playout_knobs", "check_forced_knobs", "check_fpu_knobs", "fpu_knobs_of", "policy_prune", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
            "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]
