@@ -430,8 +430,9 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  *   stats 1 and 7-8 the expand's algorithmic bytes, bench.py roofline_env)
  * 1-3 expansions whose prior took the window, the sparse and the general path (their sum: stats 0;
  *   YK_PRIOR_FAST=0 sends every one through the general path with the gather P write, =1 keeps the window
- *   and sparse paths and leaves the general path's P write unstaged; unset or anything else, the general
- *   path's P write also reads its priors from the window - still counted as general)
+ *   and sparse paths and leaves the general path's P write unstaged, =2 stages it after the dense pass; unset
+ *   or anything else, a general leaf at 10 dice also computes its priors compact-first through the window -
+ *   still counted as general)
  * 4 lock-step moves of the last batch that ran with the fast playout cap (0 with the cap off, and after yk_arena)
  * 5 root picks of the last batch that took a forced edge, 6 visits its pruning took off the recorded counts
  *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena)

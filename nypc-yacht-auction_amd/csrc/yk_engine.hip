@@ -890,6 +890,15 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
         }
         // an action's slot in the window
         const auto wslot = [&](int a) { return fast == 2 ? (a - NBID) / NCOMB : a - wbase; };
+        // 10 dice: every combination is valid and a category's block is NCOMB = 0 mod 4 entries, so the compact
+        // entries j .. j + 3 (j = 0 mod 4) are one category's consecutive actions a .. a + 3 with a = 2 mod 4
+        // (category starts are NBID + NCOMB c): two 8-byte halves of the 16-byte aligned logits row and of
+        // the window, whose base is 0 mod 8
+        static_assert(NBID % 4 == 2 && NCOMB % 4 == 0 && PI_LD % 4 == 0, "a group of four is two aligned 8-byte halves");
+        const bool score10 = valid.mode == 0 && valid.n >= 10;
+        // a general leaf's priors are then computed four compact entries per lane, into the window piece by piece
+        // and from there into q / qt
+        const bool gquad = d.prior_fast >= 3 && fast == 0 && score10 && V > 0;
         if (d.prior == 0) {
             // pi = exp(log_softmax(logits)) (NNet.py:193) at the valid actions only: the forward
             // supplies each row's (max, log sum exp), so the invalid logits are never read
@@ -912,6 +921,38 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
         } else {
             v = hash_prior_v(hsh);
         }
+        // The unnormalised priors of a 10-dice score node's compact entries [jlo, jhi) (both 0 mod 4) into the
+        // window laid out by action from wb: lane l takes the entries 4l .. 4l + 3 of each 256 - one action
+        // computation (compact_to_action's 10-dice form), two 8-byte loads of the row, four priors (the dense
+        // pass's expressions on the same operands) and two 8-byte window writes; four iterations' loads in
+        // flight per lane, no range test per entry.  Only valid actions' logits are read.
+        const auto quad_priors = [&](int jlo, int jhi, int wb) {
+            const float* __restrict__ xr = d.logits + (long)e * PI_LD;
+            for (int j0 = jlo + 4 * lane; j0 < jhi; j0 += 1024) {
+                int aa[4];
+                float2 x01[4], x23[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int j = j0 + 256 * u, ci = j / NCOMB;
+                    const bool in = j < jhi;
+                    aa[u] = in ? NBID + NCOMB * (int)((vi.cats >> (4 * ci)) & 0xF) + (j - ci * NCOMB) : NBID;
+                    x01[u] = (d.prior == 0 && in) ? *reinterpret_cast<const float2*>(xr + aa[u]) : make_float2(0.f, 0.f);
+                    x23[u] = (d.prior == 0 && in) ? *reinterpret_cast<const float2*>(xr + aa[u] + 2) : make_float2(0.f, 0.f);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (j0 + 256 * u < jhi) {
+                        float* w = win + (aa[u] - wb);
+                        if (d.prior == 0) {
+                            *reinterpret_cast<float2*>(w) = make_float2(softmax_p(x01[u].x, mx, lse), softmax_p(x01[u].y, mx, lse));
+                            *reinterpret_cast<float2*>(w + 2) = make_float2(softmax_p(x23[u].x, mx, lse), softmax_p(x23[u].y, mx, lse));
+                        } else {
+                            *reinterpret_cast<float2*>(w) = make_float2(hash_prior_pi(hsh, aa[u]), hash_prior_pi(hsh, aa[u] + 1));
+                            *reinterpret_cast<float2*>(w + 2) = make_float2(hash_prior_pi(hsh, aa[u] + 2), hash_prior_pi(hsh, aa[u] + 3));
+                        }
+                    }
+            }
+        };
         if (fast) {
             for (int i = 4 * lane; i < wlen; i += 256) *reinterpret_cast<float4*>(win + i) = make_float4(0.f, 0.f, 0.f, 0.f);
             wave_sync();
@@ -970,12 +1011,44 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
                 qt[r] = w;
             }
             masked = true;
+        } else if (gquad) {
+            // A general leaf at 10 dice: q / qt compact-first, through the window in the two pieces of the staged P
+            // write below - the actions below PW_SPLIT from window base 0 for lanes 0-31 (the left half of the
+            // pairwise tree), then the actions from PW_SPLIT on from base PW_BASE2 for lanes 32-63.  Per piece:
+            // zeros, the priors of the compact entries that fall in it, and each lane's leaf read back as the dense
+            // pass lays it out - an exp per valid action where the dense pass evaluates 52 per lane.  The group
+            // the split cuts (category PW_SPLIT_CAT's combinations 144 .. 147, PW_SPLIT_COMB = 2 mod 4 between
+            // its 8-byte halves) is computed in both pieces: either window holds all four of its actions, and
+            // no lane reads the two on the far side of the split.
+            const uint32_t un = ~valid.used & ((1u << NCAT) - 1u);
+            const int cut = (int)((un >> PW_SPLIT_CAT) & 1u);
+            const int jL = NCOMB * __builtin_popcount(un & ((1u << PW_SPLIT_CAT) - 1u)) + (cut ? (PW_SPLIT_COMB & ~3) : 0);
+            static_assert(PW_SPLIT + 2 <= PF_WCAP && ((ASIZE - PW_BASE2 + 3) & ~3) <= PF_WCAP && PW_SPLIT % 4 == 0,
+                          "the cut group and the zero fill stay inside the window");
+#pragma unroll
+            for (int pc = 0; pc < 2; pc++) {
+                const int wb = pc ? PW_BASE2 : 0, wn = pc ? ((ASIZE - PW_BASE2 + 3) & ~3) : PW_SPLIT;
+                if (pc) wave_sync();  // the first piece's reads precede the second piece's zeros
+                for (int i = 4 * lane; i < wn; i += 256) *reinterpret_cast<float4*>(win + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+                wave_sync();
+                quad_priors(pc ? jL : 0, pc ? V : jL + 4 * cut, wb);
+                wave_sync();
+                if ((lane >> 5) == pc) {
+                    const float* wl = win + (st - wb);
+#pragma unroll
+                    for (int j = 0; j < PW_GMAX; j++)
+                        q[j] = (j < PW_GMIN || j < G) ? *reinterpret_cast<const float4*>(wl + 8 * j + 4 * h)
+                                                      : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int r = 0; r < PW_TMAX; r++) qt[r] = (h == 0 && r < R) ? wl[8 * G + r] : 0.f;
+                }
+            }
+            wave_sync();  // the reads precede the staged write's stores to the window
+            masked = true;
         } else if (d.prior == 0) {
             const float* x = d.logits + (long)e * PI_LD + st;
             // score actions at 10 dice (most leaves): a group a .. a + 3 (a = 0 mod 4) holds at
             // most two categories, a's and a + 2's (category starts are 202 + 252 c = 2 mod 4)
-            static_assert(NBID % 4 == 2 && NCOMB % 4 == 0, "category starts are 2 mod 4");
-            const bool score10 = valid.mode == 0 && valid.n >= 10;
 #pragma unroll
             for (int j = 0; j < PW_GMAX; j++) {
                 const int a = st + 8 * j + 4 * h;
@@ -1104,7 +1177,7 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
             const bool staged = d.prior_fast >= 2 && !fast && V > 0;
             // 10 dice: every combination valid, a category's block is NCOMB = 0 mod 4 entries, so the
             // compact entries j .. j + 3 (j = 0 mod 4) are one category's consecutive actions
-            const bool quad = staged && valid.mode == 0 && valid.n >= 10;
+            const bool quad = staged && score10;
             // valid actions below the split (the compact order ascends by action); at 10 dice rounded down to
             // a whole group of four - the second piece's window holds the cut group's actions below the split
             int jA = 0;
@@ -2089,9 +2162,10 @@ constexpr int YK_FPARTS_MAX = 4;
         d.node_summary = (en && en[0] == '0') ? 0 : 1;
         // YK_PRIOR_FAST=0: every leaf's prior takes the dense pass and the gather P write (A/B, and the
         // test that all levels give the same trees); 1: the compact-first paths, general leaves unstaged;
-        // unset or anything else: those and the staged P write of the general leaves
+        // 2: those and the staged P write of the general leaves (dense pass kept); unset or anything else (3): a
+        // general leaf's priors at 10 dice are also computed compact-first, through the window, four per lane
         const char* ep = getenv("YK_PRIOR_FAST");
-        d.prior_fast = !ep ? 2 : (ep[0] == '0' && !ep[1]) ? 0 : (ep[0] == '1' && !ep[1]) ? 1 : 2;
+        d.prior_fast = (ep && ep[0] >= '0' && ep[0] <= '2' && !ep[1]) ? ep[0] - '0' : 3;
         // YK_SPLIT_DESCENT=1 (measurement): k_expand_backup stops after the backup and each next
         // descent is its own k_select launch, so rocprofv3 times and counts the expansion + backup
         // and the descent apart (the same work: the trees are identical)

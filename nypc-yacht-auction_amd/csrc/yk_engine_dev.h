@@ -89,11 +89,13 @@ struct EngDev {
                            //        rv (RV_OFF: no P order this move), walk start: the order's entries
                            //        before it are all visited}; one 32-byte read for root_scan
     int node_summary;      // 1: a node's first UCB scan takes the record's first_j (YK_NODE_SUMMARY=0: full scans)
-    int prior_fast;        // >= 1: a leaf with a small valid set computes its priors in compact order; 2 (the default):
+    int prior_fast;        // >= 1: a leaf with a small valid set computes its priors in compact order; >= 2:
                            //    a general leaf's P write also reads its priors back from the window, staged there in
-                           //    two pieces of the pairwise tree's leaves, four entries per lane at 10 dice
+                           //    two pieces of the pairwise tree's leaves, four entries per lane at 10 dice; 3 (the
+                           //    default): a general leaf's priors at 10 dice are computed compact-first too, through
+                           //    the window in the same two pieces, in place of the dense pass
                            //    (YK_PRIOR_FAST=0: every leaf takes the dense pass and the gather P write, =1: general
-                           //    leaves unstaged)
+                           //    leaves unstaged, =2: general leaves staged after the dense pass)
     int ro_k;              // entries of the root's order k_root_sort keeps (RO_K; YK_ROOT_K for the tests)
     uint32_t* rv;          // [T][RV_CAP] j | slot << 12 of each visited root edge
     uint16_t* ro_j;        // [T][RO_K] the root's top compact indices by descending P (ascending j on ties)
