@@ -196,6 +196,29 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
 int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
                     const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
                     const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream);
+/* The two functions above over x' instead of x (the legal-move mask): x'_a = x_a where
+ * action_valid(state r, 1, a), -inf elsewhere.  Arguments, the 16 columns, the reduction order, errors and
+ * synchronisation are theirs; column 4 is then 1, the rank in column 2 counts valid actions only, the entropy
+ * skips the terms with e_a = 0 (no 0 * -inf).  A target outside the valid set gives an infinite column 1, a
+ * state without a valid action NaN. */
+int yk_examples_metrics_legal(const float* logits, int64_t ld, const float* v, const yk_state_t* states,
+                              const int32_t* targets, const float* values, const int64_t* pi_indptr,
+                              const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
+                              double* rows, double* sums, void* stream);
+int yk_net_evaluate_legal(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                          const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                          const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream);
+/* The contract of masked training, checked on the device: row i (example r = batch_idx[i], or i) must have a
+ * valid action, its hard target (targets, may be NULL: not checked) must be valid, and every CSR entry with
+ * p > 0 (all three CSR pointers, or all NULL: not checked) must sit on a valid column.  One wavefront per row;
+ * HOST *first_bad = the lowest offending i, or -1, and HOST *kind = why: 0 clean, 1 no valid action, 2 the hard
+ * target invalid or outside 0..3225, 3 a CSR column with p > 0 invalid or outside (a row's first finding in
+ * that order).  The result is a minimum over per-block findings: no atomics, no dependence on launch order.
+ * Synchronises `stream`.  NULL states / first_bad / kind, n < 0 or > 2^31 - 1, a half-given CSR: YK_ERR_ARG before
+ * anything touches the device; n == 0: clean. */
+int yk_examples_check_legal(const yk_state_t* states, const int32_t* targets, const int64_t* pi_indptr,
+                            const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
+                            int64_t* first_bad /* HOST */, int* kind /* HOST */, void* stream);
 
 /* ---------------------------------------------------------------- weighted minibatch sampling
  * Which examples a train step sees, drawn with replacement from per-example weights: recency x policy
@@ -702,6 +725,19 @@ int64_t yk_trainer_step_count(yk_trainer_t* t);
 int yk_trainer_set_row_offset(yk_trainer_t* t, int64_t row0);
 /* HOST out[4] (amp mode): loss scale, growth tracker, optimiser steps taken, last step skipped */
 int yk_trainer_amp_state(yk_trainer_t* t, double* out);
+
+/* ---------------------------------------------------------------- legal-move mask (opt-in)
+ * on = 1: every later yk_trainer_backward / _step and both _soft forms take the policy softmax, its loss and
+ * its gradient over each row's valid actions only: L_i = {a : action_valid(states[idx[i]], 1, a)}, the logits
+ * x'_a = x_a on L_i and -inf elsewhere (float32 trainer: x_a = z[a] + bpi[a]; mixed precision: the fp16-rounded
+ * r16(acc + bias), masked after that rounding), CE = lse' - x'_t (soft: sum p_k (lse' - x'_{c_k})),
+ * dlogit_a = (s softmax(x')_a - p_a) / B - exactly 0 outside L_i.  One more launch per backward writes the
+ * rows' bits into a trainer-owned buffer (allocated by the first call with on = 1).  The caller keeps the
+ * contract yk_examples_check_legal checks; the trainer does not defend it (an empty L_i gives NaN, a target
+ * outside L_i an infinite cross-entropy).  on = 0 (the default): the launches of a trainer that never had the
+ * mask.  Trainer state, not a field of yk_train_config_t.  NULL, or on outside {0, 1}: YK_ERR_ARG, nothing on
+ * the device touched. */
+int yk_trainer_set_legal_mask(yk_trainer_t* t, int on);
 
 /* ---------------------------------------------------------------- averaged (EMA) weights (opt-in)
  * A shadow e of the trainer's flat parameter buffer p that follows it, for play and gating; a departure from

@@ -8,6 +8,7 @@
 
 #include "yk_api.h"
 #include "yk_common.h"
+#include "yk_legal.h"
 
 using namespace yk;
 
@@ -65,23 +66,13 @@ __global__ void k_step(const yk_state_t* in, const int32_t* players, const int32
     }
 }
 
-// one wavefront per state; ballot builds 64 action bits per iteration
+// one wavefront per state; ballots build 64 action bits per iteration (valid_row_bits, yk_legal.h)
 __global__ void k_valid_mask(const yk_state_t* in, const int32_t* players, uint32_t* mask, int32_t* counts, int n) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     if (i >= n) return;
     const YkS s = load_state(in, i);
-    const int pl = players[i];
-    int total = 0;
-    for (int base = 0; base < 64 * ((ASIZE + 63) / 64); base += 64) {
-        const int a = base + lane;
-        const bool v = a < ASIZE && action_valid(s, pl, a);
-        const uint64_t b = __ballot(v);
-        total += __popcll(b);
-        const int word = base / 32;
-        if (lane == 0 && word < MASK_WORDS) mask[(long)i * MASK_WORDS + word] = (uint32_t)b;
-        if (lane == 1 && word + 1 < MASK_WORDS) mask[(long)i * MASK_WORDS + word + 1] = (uint32_t)(b >> 32);
-    }
+    const int total = valid_row_bits(s, players[i], lane, mask + (long)i * MASK_WORDS);
     if (counts && lane == 0) counts[i] = total;
 }
 

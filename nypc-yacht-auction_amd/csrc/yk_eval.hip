@@ -25,6 +25,7 @@
 
 #include "yk_api.h"
 #include "yk_common.h"
+#include "yk_legal.h"
 #include "yk_net.h"
 
 using namespace yk;
@@ -54,6 +55,11 @@ __device__ __forceinline__ float row_gather(const float (&x)[PER_LANE], int c) {
 
 // One wavefront per example row, four rows per block.  Lane l keeps logits l, l + 64, ... (51 registers),
 // read once; the target's and the CSR columns' logits are taken out of those registers (row_gather).
+// MASK (yk_examples_metrics_legal / yk_net_evaluate_legal): the same columns over x', the
+// logits with -inf at the actions action_valid refuses - the predicate of column 4, which is then 1; the rank
+// counts valid actions only, and the entropy skips the terms with e_a = 0 (never 0 * -inf).  The additions
+// run in the same order, so the unmasked instantiation is the code it was.
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_eval_rows(const float* __restrict__ logits, int64_t ld,
                                                    const float* __restrict__ v, const yk_state_t* __restrict__ states,
                                                    const int32_t* __restrict__ targets,
@@ -77,6 +83,11 @@ __global__ __launch_bounds__(256) void k_eval_rows(const float* __restrict__ log
     YkS s;
 #pragma unroll
     for (int k = 0; k < 8; k++) s.w[k] = states[r].w[k];
+    if constexpr (MASK) {
+#pragma unroll
+        for (int k = 0; k < PER_LANE; k++)
+            if (!action_valid(s, 1, lane + 64 * k)) x[k] = -INFINITY;  // (past 3225 x is -inf already)
+    }
     const int t = targets[r];
     const bool t_in = t >= 0 && t < ASIZE;
     // the CSR row's bounds and its first 64 entries are asked for now: they arrive under the exp pass
@@ -113,9 +124,16 @@ __global__ __launch_bounds__(256) void k_eval_rows(const float* __restrict__ log
             const double xa = (double)x[k];
             const double e = exp(xa - m);
             se += e;
-            sex += e * xa;
-            if (action_valid(s, 1, a)) sv += e;
-            above += (x[k] > xt || (x[k] == xt && a < t)) ? 1 : 0;
+            if constexpr (MASK) {
+                const bool ok = action_valid(s, 1, a);
+                if (e > 0.0) sex += e * xa;
+                if (ok) sv += e;
+                above += (ok && (x[k] > xt || (x[k] == xt && a < t))) ? 1 : 0;
+            } else {
+                sex += e * xa;
+                if (action_valid(s, 1, a)) sv += e;
+                above += (x[k] > xt || (x[k] == xt && a < t)) ? 1 : 0;
+            }
         }
     }
     se = xlane_sum(se);
@@ -201,9 +219,13 @@ struct Csr {
 
 void launch_rows(const float* logits, int64_t ld, const float* v, const yk_state_t* states, const int32_t* targets,
                  const float* values, const Csr& p, const int32_t* batch_idx, int64_t ex0, int n, double* rows,
-                 hipStream_t s) {
-    hipLaunchKernelGGL(k_eval_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, logits, ld, v, states, targets,
-                       values, p.indptr, p.cols, p.vals, batch_idx, ex0, n, rows);
+                 bool masked, hipStream_t s) {
+    if (masked)
+        hipLaunchKernelGGL(k_eval_rows<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, logits, ld, v, states,
+                           targets, values, p.indptr, p.cols, p.vals, batch_idx, ex0, n, rows);
+    else
+        hipLaunchKernelGGL(k_eval_rows<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, logits, ld, v, states,
+                           targets, values, p.indptr, p.cols, p.vals, batch_idx, ex0, n, rows);
 }
 
 // rows[n][16] (device) -> HOST sums[16]; `work` is device scratch of (NPART + 1) * NCOL doubles
@@ -218,6 +240,76 @@ int reduce_to_host(const double* rows, int64_t n, double* work, double* sums, hi
 
 bool csr_ok(const int64_t* a, const int32_t* b, const double* c) { return (a && b && c) || (!a && !b && !c); }
 
+// ---- yk_examples_check_legal: the contract of the legal-move mask over n examples.
+// One wavefront per row, four rows per block.  A row's finding: 0 clean, 1 no valid action, 2 the hard
+// target invalid or outside 0..3225, 3 a CSR entry with p > 0 whose column is invalid (or outside).  Block b
+// writes code[b] = 4 * (its lowest offending row) + kind, or INT64_MAX; k_check_min takes the minimum of the
+// codes - a minimum does not depend on the order, and no atomics touch data.
+constexpr int64_t CLEAN = INT64_MAX;
+__global__ __launch_bounds__(256) void k_check_legal(const yk_state_t* __restrict__ states,
+                                                     const int32_t* __restrict__ targets,
+                                                     const int64_t* __restrict__ indptr,
+                                                     const int32_t* __restrict__ cols, const double* __restrict__ vals,
+                                                     const int32_t* __restrict__ batch_idx, int n,
+                                                     int64_t* __restrict__ code) {
+    __shared__ int kinds[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + wave));
+    int kind = 0;
+    if (row < n) {
+        const int64_t r = batch_idx ? (int64_t)batch_idx[row] : row;
+        YkS s;
+#pragma unroll
+        for (int k = 0; k < 8; k++) s.w[k] = states[r].w[k];
+        if (valid_row_bits<false>(s, 1, lane, nullptr) == 0) {
+            kind = 1;
+        } else {
+            if (targets) {
+                const int t = targets[r];
+                if (t < 0 || t >= ASIZE || !action_valid(s, 1, t)) kind = 2;
+            }
+            if (kind == 0 && indptr) {
+                const int64_t a1 = indptr[r + 1];
+                bool bad = false;
+                for (int64_t k = indptr[r] + lane; k < a1; k += 64) {
+                    const int c = cols[k];
+                    if (vals[k] > 0.0 && (c < 0 || c >= ASIZE || !action_valid(s, 1, c))) bad = true;
+                }
+                if (__ballot(bad)) kind = 3;
+            }
+        }
+    }
+    if (lane == 0) kinds[wave] = kind;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t c = CLEAN;
+        for (int w = 3; w >= 0; w--)
+            if (kinds[w]) c = 4 * ((int64_t)blockIdx.x * 4 + w) + kinds[w];
+        code[blockIdx.x] = c;
+    }
+}
+// out[0] = min of code[0 .. nb - 1]: thread t takes codes t, t + 256, ..., then a tree over the 256
+__global__ __launch_bounds__(256) void k_check_min(const int64_t* __restrict__ code, int64_t nb,
+                                                   int64_t* __restrict__ out) {
+    __shared__ int64_t part[256];
+    int64_t m = CLEAN;
+    for (int64_t i = threadIdx.x; i < nb; i += 256) m = code[i] < m ? code[i] : m;
+    part[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o && part[threadIdx.x + o] < part[threadIdx.x]) part[threadIdx.x] = part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = part[0];
+}
+
+int metrics_impl(const float* logits, int64_t ld, const float* v, const yk_state_t* states, const int32_t* targets,
+                 const float* values, const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                 const int32_t* batch_idx, int64_t n, double* rows, double* sums, bool masked, void* stream);
+int evaluate_impl(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                  const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx,
+                  int64_t n, int chunk, double* rows, double* sums, bool masked, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -231,6 +323,70 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
                         const int32_t* targets, const float* values, const int64_t* pi_indptr,
                         const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
                         double* rows, double* sums, void* stream) {
+    return metrics_impl(logits, ld, v, states, targets, values, pi_indptr, pi_cols, pi_vals, batch_idx, n, rows, sums,
+                        false, stream);
+}
+
+int yk_examples_metrics_legal(const float* logits, int64_t ld, const float* v, const yk_state_t* states,
+                              const int32_t* targets, const float* values, const int64_t* pi_indptr,
+                              const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
+                              double* rows, double* sums, void* stream) {
+    return metrics_impl(logits, ld, v, states, targets, values, pi_indptr, pi_cols, pi_vals, batch_idx, n, rows, sums,
+                        true, stream);
+}
+
+int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                    const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                    const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream) {
+    return evaluate_impl(net, states, targets, values, pi_indptr, pi_cols, pi_vals, batch_idx, n, chunk, rows, sums,
+                         false, stream);
+}
+
+int yk_net_evaluate_legal(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                          const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                          const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream) {
+    return evaluate_impl(net, states, targets, values, pi_indptr, pi_cols, pi_vals, batch_idx, n, chunk, rows, sums,
+                         true, stream);
+}
+
+int yk_examples_check_legal(const yk_state_t* states, const int32_t* targets, const int64_t* pi_indptr,
+                            const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx, int64_t n,
+                            int64_t* first_bad, int* kind, void* stream) {
+    if (!states || !first_bad || !kind || n < 0 || n > INT32_MAX || !csr_ok(pi_indptr, pi_cols, pi_vals))
+        return YK_ERR_ARG;
+    *first_bad = -1;
+    *kind = 0;
+    if (n == 0) return YK_OK;
+    hipStream_t s = as_stream(stream);
+    const int64_t nb = (n + 3) / 4;
+    Scratch buf(s);
+    YK_TRY(buf.alloc(sizeof(int64_t) * (size_t)(nb + 1)));
+    int64_t* code = buf.as<int64_t>();
+    hipLaunchKernelGGL(k_check_legal, dim3((unsigned)nb), dim3(256), 0, s, states, targets, pi_indptr, pi_cols, pi_vals,
+                       batch_idx, (int)n, code);
+    int rc = launched();
+    if (rc == YK_OK) {
+        hipLaunchKernelGGL(k_check_min, dim3(1), dim3(256), 0, s, code, nb, code + nb);
+        rc = launched();
+    }
+    int64_t c = CLEAN;
+    if (rc == YK_OK) rc = hip_rc(hipMemcpyAsync(&c, code + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    (void)buf.release();
+    YK_HIP(hipStreamSynchronize(s));
+    if (rc == YK_OK && c != CLEAN) {
+        *first_bad = c / 4;
+        *kind = (int)(c % 4);
+    }
+    return rc;
+}
+
+}  // extern "C"
+
+namespace {
+
+int metrics_impl(const float* logits, int64_t ld, const float* v, const yk_state_t* states, const int32_t* targets,
+                 const float* values, const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
+                 const int32_t* batch_idx, int64_t n, double* rows, double* sums, bool masked, void* stream) {
     if (!logits || !v || !states || !targets || !values || !sums || n < 0 || n > INT32_MAX || ld < ASIZE ||
         !csr_ok(pi_indptr, pi_cols, pi_vals))
         return YK_ERR_ARG;
@@ -243,7 +399,7 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
     double* work = buf.as<double>();
     double* out = rows ? rows : work + nwork;
     launch_rows(logits, ld, v, states, targets, values, Csr{pi_indptr, pi_cols, pi_vals}, batch_idx, 0, (int)n, out,
-                s);
+                masked, s);
     int rc = launched();
     if (rc == YK_OK) rc = reduce_to_host(out, n, work, sums, s);
     (void)buf.release();
@@ -251,9 +407,9 @@ int yk_examples_metrics(const float* logits, int64_t ld, const float* v, const y
     return rc;
 }
 
-int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
-                    const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals,
-                    const int32_t* batch_idx, int64_t n, int chunk, double* rows, double* sums, void* stream) {
+int evaluate_impl(yk_net_t* net, const yk_state_t* states, const int32_t* targets, const float* values,
+                  const int64_t* pi_indptr, const int32_t* pi_cols, const double* pi_vals, const int32_t* batch_idx,
+                  int64_t n, int chunk, double* rows, double* sums, bool masked, void* stream) {
     if (!net || !states || !targets || !values || !sums || n < 0 || n > INT32_MAX ||
         !csr_ok(pi_indptr, pi_cols, pi_vals))
         return YK_ERR_ARG;
@@ -277,7 +433,7 @@ int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targ
         const int32_t* idx = batch_idx ? batch_idx + c0 : nullptr;
         rc = launch_forward(net->dev, idx ? states : states + c0, nullptr, idx, nullptr, m, logits, v, s);
         if (rc != YK_OK) break;
-        launch_rows(logits, PI_LD, v, states, targets, values, p, idx, c0, m, out + c0 * NCOL, s);
+        launch_rows(logits, PI_LD, v, states, targets, values, p, idx, c0, m, out + c0 * NCOL, masked, s);
         rc = launched();
     }
     if (rc == YK_OK) rc = reduce_to_host(out, n, work, sums, s);
@@ -286,4 +442,4 @@ int yk_net_evaluate(yk_net_t* net, const yk_state_t* states, const int32_t* targ
     return rc;
 }
 
-}  // extern "C"
+}  // namespace

@@ -20,6 +20,7 @@
 
 #include "yk_api.h"
 #include "yk_common.h"
+#include "yk_legal.h"
 #include "yk_train_amp.h"
 
 using namespace yk;
@@ -197,11 +198,27 @@ struct SoftRows {
 };
 template <bool SOFT>
 using LossTgt = std::conditional_t<SOFT, SoftRows, const int32_t*>;
-template <bool SOFT>
+// MASK (yk_trainer_set_legal_mask): the logits of the row's invalid actions are -inf
+// where x is made - the softmax, the loss and dlogits are then those of the valid actions alone, and
+// dlogits is exactly 0 elsewhere (expf(-inf - lse) = 0).  The bits ride with the target argument
+// (k_legal_bits wrote them), so without MASK the kernel and its arguments are what they were.
+template <class Tgt>
+struct LegalTgt {
+    Tgt t;
+    const uint32_t* legal;  // [B][LEGAL_LD], bit a & 31 of word a >> 5: action a is valid in the row
+};
+template <bool SOFT, bool MASK>
+using LossArg = std::conditional_t<MASK, LegalTgt<LossTgt<SOFT>>, LossTgt<SOFT>>;
+template <class Tgt>
+__device__ __forceinline__ const Tgt& loss_tgt(const Tgt& a) { return a; }
+template <class Tgt>
+__device__ __forceinline__ const Tgt& loss_tgt(const LegalTgt<Tgt>& a) { return a.t; }
+template <bool SOFT, bool MASK = false>
 __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const float* bpi, float* Zv1, const float* bv1,
-                                                 const float* wv2, const float* bv2, LossTgt<SOFT> tgt,
+                                                 const float* wv2, const float* bv2, LossArg<SOFT, MASK> targ,
                                                  const float* vt, float* dlogits, float* dZv1, float* dzv2,
                                                  float* v2prod, float* vout, float2* lrow, int B, int A, float vw) {
+    const LossTgt<SOFT>& tgt = loss_tgt(targ);
     __shared__ float red[2][LOSS_T / 64];
     __shared__ float pd[SOFT ? ASIZE : 1];  // SOFT: the row's dense target
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -219,7 +236,10 @@ __global__ __launch_bounds__(LOSS_T) void k_loss(const float* logits, const floa
 #pragma unroll
     for (int k = 0; k < LOSS_NV; k++) {
         const int a = tid + LOSS_T * k;
-        x[k] = a < A ? z[a] + bpi[a] : -INFINITY;
+        if constexpr (MASK)
+            x[k] = a < A && ((targ.legal[(long)row * LEGAL_LD + (a >> 5)] >> (a & 31)) & 1u) ? z[a] + bpi[a] : -INFINITY;
+        else
+            x[k] = a < A ? z[a] + bpi[a] : -INFINITY;
         m = fmaxf(m, x[k]);
     }
     m = wmax(m);
@@ -460,6 +480,20 @@ __global__ void k_gather_soft(const yk_state_t* states, SoftCsr csr, const float
         vt[i] = v_all[src];
     }
 }
+// the legal-move mask's bits (yk_trainer_set_legal_mask): row i of legal[B][LEGAL_LD] = the valid
+// actions of player 1 on the canonical board states[idx[i]].  One workgroup per row, its four waves taking
+// every fourth 64-action ballot of valid_row_bits: the 51 ballots of a row depend on one another through
+// nothing but the loop, and a wave per row ran them one after the other (15 us at batch 512; 13 deep: 5 us)
+__global__ __launch_bounds__(256) void k_legal_bits(const yk_state_t* states, const int32_t* idx, uint32_t* legal,
+                                                    int B) {
+    const int row = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (row >= B) return;
+    const int src = idx ? idx[row] : row;
+    YkS s;
+#pragma unroll
+    for (int k = 0; k < 8; k++) s.w[k] = states[src].w[k];
+    valid_row_bits(s, 1, lane, legal + (long)row * LEGAL_LD, wave, 4);
+}
 // sum of squares of the gradient buffer: one double partial per workgroup (no atomics); k_adamw
 // adds the SQ_BLOCKS partials in a fixed order
 constexpr int SQ_BLOCKS = 1024;
@@ -568,6 +602,10 @@ struct yk_trainer {
     double ema_decay = 0.0;
     int ema_every = 1;
     int64_t ema_updates = 0, ema_since = 0;  // updates made; applies since the last one
+    // legal-move mask (yk_trainer_set_legal_mask): the batch rows' valid-action bits [Bmax][LEGAL_LD], allocated
+    // by the first call that turns the mask on and kept in `mem`; every masked backward fills it (k_legal_bits)
+    uint32_t* legal = nullptr;
+    bool legal_on = false;
     yk_trainer() = default;
     yk_trainer(const yk_trainer&) = delete;
     yk_trainer& operator=(const yk_trainer&) = delete;
@@ -769,7 +807,18 @@ int step_impl(yk_trainer* t, const yk_state_t* states, const int32_t* targets, c
     YK_LAUNCHED();
     if ((rc = gemm_rm(s, t->gws, false, true, B, A, H, t->Api, H, Pt(t_head(NB, 2)), H, t->logits, A, 0.f))) return rc;
     if ((rc = gemm_rm(s, t->gws, false, true, B, 128, H, t->Av, H, Pt(t_head(NB, 6)), H, t->Zv1, 128, 0.f))) return rc;
-    if (soft)
+    if (t->legal_on) {  // the masked forms: the same launches, the row's bits beside the target
+        if (soft)
+            hipLaunchKernelGGL((k_loss<true, true>), dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1,
+                               Pt(t_head(NB, 7)), Pt(t_head(NB, 8)), Pt(t_head(NB, 9)),
+                               LegalTgt<SoftRows>{SoftRows{sv, idx}, t->legal}, t->vt, t->dlogits, t->dZv1, t->dzv2,
+                               t->v2prod, t->vout, t->lrow, B, A, t->cfg.vloss_weight);
+        else
+            hipLaunchKernelGGL((k_loss<false, true>), dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1,
+                               Pt(t_head(NB, 7)), Pt(t_head(NB, 8)), Pt(t_head(NB, 9)),
+                               LegalTgt<const int32_t*>{t->tgt, t->legal}, t->vt, t->dlogits, t->dZv1, t->dzv2,
+                               t->v2prod, t->vout, t->lrow, B, A, t->cfg.vloss_weight);
+    } else if (soft)
         hipLaunchKernelGGL(k_loss<true>, dim3(B), dim3(LOSS_T), 0, s, t->logits, Pt(t_head(NB, 3)), t->Zv1,
                            Pt(t_head(NB, 7)), Pt(t_head(NB, 8)), Pt(t_head(NB, 9)), SoftRows{sv, idx}, t->vt,
                            t->dlogits, t->dZv1, t->dzv2, t->v2prod, t->vout, t->lrow, B, A, t->cfg.vloss_weight);
@@ -965,9 +1014,14 @@ int yk_trainer_buffers(yk_trainer_t* t, float** params, float** grads, int64_t* 
 // targets: the hard labels, or - soft given - unused (the CSR's visit policies are the targets)
 static int backward_impl(yk_trainer_t* t, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
                          const float* values, const int32_t* batch_idx, int batch, bool fuse_norm, hipStream_t s) {
+    if (t->legal_on) {  // the one extra launch of a masked step, ahead of whichever head kernel reads the bits
+        hipLaunchKernelGGL(k_legal_bits, dim3(batch), dim3(256), 0, s, states, batch_idx, t->legal, batch);
+        YK_LAUNCHED();
+    }
     if (t->amp)
         return yk::amp_backward(t->amp, states, targets, soft, values, batch_idx, batch, t->cfg.dropout, t->cfg.seed,
-                                t->step, t->row_base, t->cfg.vloss_weight, fuse_norm, s);
+                                t->step, t->row_base, t->cfg.vloss_weight, fuse_norm, t->legal_on ? t->legal : nullptr,
+                                s);
     switch (t->H) {
         case 64: return step_impl<1>(t, states, targets, soft, values, batch_idx, batch, s);
         case 128: return step_impl<2>(t, states, targets, soft, values, batch_idx, batch, s);
@@ -1132,6 +1186,18 @@ int yk_trainer_set_row_offset(yk_trainer_t* t, int64_t row0) {
 int yk_trainer_amp_state(yk_trainer_t* t, double* out) {
     if (!t || !out || !t->amp) return YK_ERR_ARG;
     return yk::amp_state(t->amp, out);
+}
+
+// ---------------------------------------------------------------- legal-move mask
+int yk_trainer_set_legal_mask(yk_trainer_t* t, int on) {
+    if (!t || (on != 0 && on != 1)) return YK_ERR_ARG;
+    if (on && !t->legal) {  // (zeroed once: the words past MASK_WORDS of a row are never written)
+        YK_TRY(t->mem.alloc(&t->legal, (size_t)t->Bmax * LEGAL_LD));
+        YK_HIP(hipMemset(t->legal, 0, sizeof(uint32_t) * (size_t)t->Bmax * LEGAL_LD));
+        YK_HIP(hipDeviceSynchronize());
+    }
+    t->legal_on = on == 1;
+    return YK_OK;
 }
 
 // ---------------------------------------------------------------- averaged weights

@@ -54,10 +54,11 @@ int amp_pack(AmpTrain* a, hipStream_t s);
 // gradient launches also sum the unscaled sq-norm, and the next amp_apply uses it instead of
 // re-reading G (only when nothing changes G in between: yk_trainer_step, not the DDP split).
 // soft: the visit policies as targets (cross-entropy with probability targets; `targets` unused),
-// or null for the hard labels.
+// or null for the hard labels.  legal: the batch rows' valid-action bits [B][LEGAL_LD] (yk_legal.h; the
+// legal-move mask: an invalid action's fp16 logit becomes -inf where k_amp_head makes it), or null.
 int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
                  const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
-                 float vloss_weight, bool fuse_norm, hipStream_t s);
+                 float vloss_weight, bool fuse_norm, const uint32_t* legal, hipStream_t s);
 // GradScaler.unscale_ + clip_grad_norm_(max_norm) + AdamW step (skipped, with the scale halved,
 // when a gradient is inf / nan) + GradScaler.update + fp16 repack.  sq_out: the unscaled grad
 // sq-norm (double).  dropout / seed / next_step: the next backward's dropout draws, which the

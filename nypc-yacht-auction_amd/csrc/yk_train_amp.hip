@@ -40,6 +40,7 @@
 
 #include "yk_api.h"
 #include "yk_common.h"
+#include "yk_legal.h"
 #include "yk_train_amp.h"
 
 using namespace yk;
@@ -645,11 +646,38 @@ __device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int la
     }
 }
 
+// The legal-move mask (yk_trainer_set_legal_mask): LegalBits at the head of the pack.
+// A masked column's logit is stored as -inf - after the fp16 rounding - and takes no part in the running
+// (max, sum exp): with x = m = -inf the update would take exp(NaN), so the bit guards the whole update, and
+// a part (or a wave's share of one) without a valid column leaves (-inf, 0), which stat_merge passes over.
+// The tile's 16 rows x the part's mask words go through LDS once per workgroup, before the tile loop and
+// before the first weight slice is asked for: a load inside do_tile would sit behind the next tile's
+// slices in the in-order wait counter.  Everything after the logits needs no change: expf(-inf - lse) = 0
+// in k_amp_headbwd, the targets' terms are 0 at masked columns, so dlogits is exactly 0 there.
+struct LegalBits {
+    const uint32_t* __restrict__ w;  // [B][LEGAL_LD]
+};
+template <class... E>
+struct legal_first : std::false_type {};
+template <class... R>
+struct legal_first<LegalBits, R...> : std::true_type {};
+template <class... R>
+__device__ __forceinline__ const uint32_t* legal_words(const LegalBits& l, const R&...) { return l.w; }
+template <class... R>
+__device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int lane, const LegalBits&, const R&... r) {
+    soft_tile_prep(row0, B, wave, lane, r...);
+}
+constexpr int LMW = 17;  // mask words per row in LDS: a part's <= 26 column tiles span <= 14 words; odd stride
+static_assert(((PT + HQ - 1) / HQ * 16 + 16 + 31) / 32 <= LMW, "a head part's mask words");
+
 template <int H, class... Soft>
 __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft) {
     constexpr int SA = H + 8, KS = H / 32;
+    constexpr bool MASK = legal_first<Soft...>::value;
+    constexpr int NSOFT = (int)sizeof...(Soft) - (MASK ? 1 : 0);
     __shared__ __attribute__((aligned(16))) _Float16 A[TR * SA];
     __shared__ float2 red[TW][TR];
+    __shared__ uint32_t LM[MASK ? TR * LMW : 1];  // MASK: the tile's rows' mask words from word lw0 on
     const int tile = blockIdx.x, part = blockIdx.y, row0 = tile * TR;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4;
     const bool vpart = part == HQ;
@@ -659,6 +687,17 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft
         const float4 v = row0 + r < B ? reinterpret_cast<const float4*>(src + (long)(row0 + r) * H)[c8]
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(A + r * SA + 8 * c8) = v;
+    }
+    int lw0 = 0;  // MASK: the part's first mask word
+    if constexpr (MASK) {
+        lw0 = (16 * (part * PT / HQ)) >> 5;
+        if (!vpart) {
+            const uint32_t* lw = legal_words(soft...);
+            for (int i = tid; i < TR * LMW; i += TTHR) {
+                const int r = i / LMW, w = lw0 + i % LMW;
+                LM[i] = row0 + r < B && w < LEGAL_LD ? lw[(long)(row0 + r) * LEGAL_LD + w] : 0u;
+            }
+        }
     }
     __syncthreads();
     const _Float16* ap = A + (lane & 15) * SA + 8 * (lane >> 4);
@@ -675,7 +714,7 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft
             const int row = row0 + 4 * q + j;
             if (row < B) d.zv1[(long)row * VH + col] = r16(acc[j] + bias);
         }
-        if constexpr (sizeof...(Soft) > 0) soft_tile_prep(row0, B, wave, lane, soft...);
+        if constexpr (NSOFT > 0) soft_tile_prep(row0, B, wave, lane, soft...);
         return;
     }
     const int t0 = part * PT / HQ, t1 = (part + 1) * PT / HQ;
@@ -703,8 +742,14 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int row = row0 + 4 * q + j;
-                const float x = r16(acc[j] + bias);
+                float x = r16(acc[j] + bias);
+                bool on = true;
+                if constexpr (MASK) {
+                    on = (LM[(4 * q + j) * LMW + (col >> 5) - lw0] >> (col & 31)) & 1u;
+                    x = on ? x : -INFINITY;
+                }
                 if (row < B) d.logits[(long)row * LDL + col] = x;
+                if (!on) continue;
                 if (x > m[j]) {
                     s[j] = s[j] * __expf(m[j] - x) + 1.0f;
                     m[j] = x;
@@ -1929,8 +1974,9 @@ int amp_pack(AmpTrain* a, hipStream_t s) {
 
 int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, const SoftCsr* soft,
                  const float* values, const int32_t* idx, int B, float dropout, uint64_t seed, uint64_t step, int64_t row_base,
-                 float vloss_weight, bool fuse_norm, hipStream_t s) {
+                 float vloss_weight, bool fuse_norm, const uint32_t* legal, hipStream_t s) {
     if (B <= 0 || B > a->Bmax) return YK_ERR_ARG;
+    const LegalBits lb{legal};
     a->norm_ready = false;
     SoftCsr sv{};  // the soft launches' argument: the caller's CSR and this trainer's per-row scratch
     if (soft) {
@@ -1955,7 +2001,12 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
     case HH:                                                                                                        \
         hipLaunchKernelGGL(k_amp_fwd<HH>, dim3(TT), dim3(TTHR), 0, s, d, states, idx, B, dropout, seed, step, row_base); \
         YK_LAUNCHED();                                                                                              \
-        if (soft)                                                                                                   \
+        if (legal && soft)                                                                                          \
+            hipLaunchKernelGGL((k_amp_head<HH, LegalBits, SoftCsr, const int32_t*>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, \
+                               B, lb, sv, idx);                                                                     \
+        else if (legal)                                                                                             \
+            hipLaunchKernelGGL((k_amp_head<HH, LegalBits>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, lb);           \
+        else if (soft)                                                                                              \
             hipLaunchKernelGGL((k_amp_head<HH, SoftCsr, const int32_t*>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, sv, idx); \
         else                                                                                                        \
             hipLaunchKernelGGL(k_amp_head<HH>, dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B);                           \

@@ -144,13 +144,18 @@ SIGNATURES = {
     "yk_trainer_ema_get": [P, P],
     "yk_trainer_ema_set": [P, P, C.c_int64],
     "yk_trainer_ema_state": [P, P],
+    "yk_trainer_set_legal_mask": [P, I],
+    "yk_examples_check_legal": [P, P, P, P, P, P, C.c_int64, P, P, P],
+    "yk_examples_metrics_legal": [P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int64, P, P, P],
+    "yk_net_evaluate_legal": [P, P, P, P, P, P, P, P, C.c_int64, I, P, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
 # search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap, the
-# averaged weights, the forced playouts and the first-play urgency (A/B baselines may predate them)
+# averaged weights, the forced playouts, the first-play urgency and the legal-move mask (A/B baselines may
+# predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
@@ -158,7 +163,8 @@ _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk
           "yk_engine_root_prior", "yk_engine_set_playout_cap", "yk_playout_schedule", "yk_examples_full_rows",
           "yk_policies_take", "yk_ema_weight", "yk_ema_update", "yk_trainer_set_ema", "yk_trainer_ema_buffer",
           "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state", "yk_engine_set_forced_playouts",
-          "yk_policy_prune", "yk_engine_set_fpu", "yk_fpu_pick"}
+          "yk_policy_prune", "yk_engine_set_fpu", "yk_fpu_pick", "yk_trainer_set_legal_mask",
+          "yk_examples_check_legal", "yk_examples_metrics_legal", "yk_net_evaluate_legal"}
 _lib = None
 
 

@@ -115,6 +115,10 @@ class Coach:
         # net that plays, gates and reanalyses is the averaged one (NNetWrapper.yk_net); learn's flow is unchanged
         from .replay import check_ema_knobs
         self.ema_decay, self.ema_every = check_ema_knobs(args.get("emaDecay", 0.0), args.get("emaEvery", 1))
+        # legal-move mask: NNetWrapper's knob, checked here as well.  With it set train minimises
+        # the valid-only cross-entropy, and the held-out line compares the nets on that loss
+        from .replay import check_mask_knobs
+        self.mask_illegal = check_mask_knobs(args.get("maskIllegal", False))
         # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims); with forcedPlayoutsK also
         # {"forced_picks", "pruned_visits"} and with fpuReduction {"fpu_unvisited_picks", "fpu_picks"} (this rank's)
         self.last_selfplay = None
@@ -293,6 +297,8 @@ class Coach:
                 if self.ema_decay > 0.0:  # what the average does: the same examples under the raw iterate
                     self.last_eval["new_raw"] = self.nnet.evaluate(self.holdoutHistory, weights="raw")
                     raw = " ; NEW raw loss %.4f" % self.last_eval["new_raw"]["loss"]
+                if self.mask_illegal:  # (evaluate follows args.maskIllegal: the loss being trained)
+                    raw += " ; policy terms over the valid actions only (maskIllegal)"
                 log.info("HELD-OUT %d examples, PREV / NEW : loss %.4f / %.4f ; policy_ce %.4f / %.4f ; top1 %.4f / "
                          "%.4f ; value_mse %.4f / %.4f%s" % (ne["n"], pe["loss"], ne["loss"], pe["policy_ce"],
                                                             ne["policy_ce"], pe["top1"], ne["top1"],

@@ -6,7 +6,8 @@ policy) and the value against the outcome.  CKPT is a checkpoint in the referenc
 (``NNetWrapper.save_checkpoint``; its ``args`` entry gives the net's size), FILE an examples file in either
 format (examples_io: this framework's ``.npz``, or the reference's pickle, read without running code from it).
 ``--weights ema`` scores the checkpoint's averaged weights (its ``ema_state_dict`` entry, written when the run
-had ``emaDecay`` set) instead of its ``state_dict``.
+had ``emaDecay`` set) instead of its ``state_dict``.  ``--masked`` gives the policy numbers over each example's valid actions only
+(the legal-move mask); without it they follow the checkpoint's ``maskIllegal``.
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ def load_examples_file(path: str):
     return load_examples(path) if zipfile.is_zipfile(path) else load_reference_examples(path)
 
 
-def evaluate_files(model: str, examples: str, target: str = None, weights: str = "raw") -> dict:
+def evaluate_files(model: str, examples: str, target: str = None, weights: str = "raw", masked=None) -> dict:
     import torch
 
     from .game import YachtGame
@@ -43,7 +44,7 @@ def evaluate_files(model: str, examples: str, target: str = None, weights: str =
     target = net.eval_target(target)  # (a bad name fails before the file is read)
     if weights == "ema":
         net._set_shadow(ck["ema_state_dict"], int(ck.get("ema_updates", 0)))
-    return net.evaluate(load_examples_file(examples), target=target, weights=weights)
+    return net.evaluate(load_examples_file(examples), target=target, weights=weights, masked=masked)
 
 
 def main(argv=None) -> int:
@@ -55,9 +56,12 @@ def main(argv=None) -> int:
                     help="the policy term of `loss` (default: the checkpoint's policy_target, else argmax)")
     ap.add_argument("--weights", choices=("raw", "ema"), default="raw",
                     help="raw: the checkpoint's state_dict (default); ema: its averaged weights (ema_state_dict)")
+    ap.add_argument("--masked", action="store_true", default=None,
+                    help="policy numbers over each example's valid actions only (default: the checkpoint's "
+                         "maskIllegal, else off)")
     a = ap.parse_args(argv)
     try:
-        out = evaluate_files(a.model, a.examples, a.target, a.weights)
+        out = evaluate_files(a.model, a.examples, a.target, a.weights, a.masked)
     except KeyError as e:
         ap.error(e.args[0])
     print(json.dumps(out))

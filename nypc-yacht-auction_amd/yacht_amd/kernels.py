@@ -223,6 +223,31 @@ def augment_examples(states, targets, policies, seed: int, epoch_key: int, symme
         ((indptr, o_pol[1], o_pol[2]) if policies is not None else None)
 
 
+# ---------------------------------------------------------------- legal-move mask
+LEGAL_KINDS = {1: "the state has no valid action", 2: "the hard target is not a valid action",
+               3: "a policy entry with p > 0 sits on an invalid action"}
+
+
+def check_legal(states, targets=None, policies=None, idx=None):
+    """The contract of masked training over examples (yk_examples_check_legal): every row has a valid action,
+    its hard target (targets int32[N], or None: not checked) is valid, and every entry with p > 0 of its policy
+    row (the device CSR, or None: not checked) sits on a valid action.  idx int32[n]: the rows to check (all
+    when None).  Returns (first_bad, kind): (-1, 0) when clean, else the lowest offending position and a key of
+    LEGAL_KINDS.  Synchronises."""
+    import ctypes as C
+    st =_dev(states, torch.int64).reshape(-1, 8)
+    n = int(idx.numel()) if idx is not None else st.shape[0]
+    tg = None if targets is None else _dev(targets, torch.int32)
+    csr = [None, None, None]
+    if policies is not None:
+        indptr, cols, vals = _csr(policies)
+        csr = [ptr(indptr), ptr(cols) or ptr(indptr), ptr(vals) or ptr(indptr)]
+    bad, kind = C.c_int64(-1), C.c_int(0)
+    call("yk_examples_check_legal", ptr(st), None if tg is None else ptr(tg), *csr,
+         None if idx is None else ptr(_dev(idx, torch.int32)), n, C.byref(bad), C.byref(kind), stream_ptr())
+    return int(bad.value), int(kind.value)
+
+
 # ---------------------------------------------------------------- weighted minibatch sampling (DESIGN.md 7b-samp)
 def sample_weights(rows, seg_lens, seg_factors, surprise: float):
     """Per-example sampling weights (yk_sample_weights): w[i] = seg_factors[segment of i] * s_i over the

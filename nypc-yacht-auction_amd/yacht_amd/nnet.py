@@ -188,18 +188,25 @@ class YkNet:
             call("yk_net_logits", self.handle, ptr(states.contiguous()), ptr(logits), ptr(v), n, stream_ptr())
         return logits, v
 
-    def evaluate(self, states, targets, values, policies=None, idx=None, chunk=0, per_row=False) -> dict:
+    def evaluate(self, states, targets, values, policies=None, idx=None, chunk=0, per_row=False,
+                 masked=False) -> dict:
         """Forward-only, dropout-free metrics of this net on examples (yk_net_evaluate):
         device states int64[N, 8], targets int32[N], values f32[N], optionally the policies' CSR
         (pi_indptr int64[N + 1], pi_cols int32, pi_vals float64) and idx int32[n], the examples to take
         (all N when None).  Returns eval_summary of the column sums; per_row adds ``rows``, the device
-        float64 [n, 16] columns.  `chunk` rows per forward (0: 16384) - the result does not depend on it."""
+        float64 [n, 16] columns.  `chunk` rows per forward (0: 16384) - the result does not depend on it.
+        masked: the same numbers over the logits with -inf at each example's invalid actions
+        (yk_net_evaluate_legal, DESIGN.md 7b-mask) - what a net trained with the legal-move mask minimises;
+        valid_mass is then 1."""
+        from .replay import check_mask_knobs
+        masked = check_mask_knobs(masked)
         csr = check_eval_args(states, targets, values, policies, idx, chunk)
         n = int(idx.numel()) if idx is not None else int(states.shape[0])
         rows = torch.empty((n, EVAL_COLS), dtype=torch.float64, device="cuda") if per_row else None
         sums = (C.c_double * EVAL_COLS)()
         if n:
-            call("yk_net_evaluate", self.handle, ptr(states), ptr(targets), ptr(values),
+            call("yk_net_evaluate_legal" if masked else "yk_net_evaluate", self.handle, ptr(states), ptr(targets),
+                 ptr(values),
                  *([ptr(t) for t in csr] if csr else [None, None, None]),
                  ptr(idx) if idx is not None else None, n, int(chunk), ptr(rows) if per_row else None, sums,
                  stream_ptr())
@@ -293,7 +300,12 @@ class NNetWrapper:
             raise ValueError(f"policy_target must be argmax or visits, not {target!r}")
         return target
 
-    def evaluate(self, examples, target=None, weights=None) -> dict:
+    def mask_on(self) -> bool:
+        """args.maskIllegal (check_mask_knobs): train on the valid-only softmax."""
+        from .replay import check_mask_knobs
+        return check_mask_knobs(self.args.get("maskIllegal", False))
+
+    def evaluate(self, examples, target=None, weights=None, masked=None) -> dict:
         """Forward only, dropout off: YkNet.evaluate's numbers for this net on `examples` - every form
         train takes (tuples, an ExampleShard, a list of either).  The values are always the outcome
         (a shard's ``outcomes``, never its knob-dependent ``values``), so runs with different valueMix /
@@ -301,9 +313,12 @@ class NNetWrapper:
         term being policy_ce, or policy_ce_soft when `target` (default args.policy_target) is "visits" -
         which needs the policies, as train does; with "argmax" the soft entries are None when the
         examples carry no policies.  `weights`: "ema" (default; the weights that play - the averaged ones with
-        args.emaDecay, else the raw ones) or "raw" (self.nnet, the optimiser's iterate)."""
-        from .replay import as_device_examples, as_device_policies
+        args.emaDecay, else the raw ones) or "raw" (self.nnet, the optimiser's iterate).  `masked`: the policy
+        numbers over each example's valid actions only (YkNet.evaluate's masked form); None (default) follows
+        args.maskIllegal, so `loss` is the loss being trained.  The dict's ``masked`` says which form it is."""
+        from .replay import as_device_examples, as_device_policies, check_mask_knobs
         target = self.eval_target(target)
+        masked = self.mask_on() if masked is None else check_mask_knobs(masked)
         if weights not in (None, "ema", "raw"):
             raise ValueError(f"weights must be ema or raw, not {weights!r}")
         states, targets, values = as_device_examples(examples, outcomes=True)
@@ -313,9 +328,10 @@ class NNetWrapper:
             if target == "visits":
                 raise
             policies = None
-        out = self.yk_net(raw=weights == "raw").evaluate(states, targets, values, policies=policies)
+        out = self.yk_net(raw=weights == "raw").evaluate(states, targets, values, policies=policies, masked=masked)
         term = out["policy_ce_soft"] if target == "visits" else out["policy_ce"]
         out["loss"] = term + float(self.args.get("vloss_weight", 1.0)) * out["value_mse"]
+        out["masked"] = masked
         return out
 
     # ---- training (NNet.py:118-174) on the native trainer (yacht_amd/train.py)
@@ -334,7 +350,7 @@ class NNetWrapper:
             self._tr = Trainer(self.nnet.state_dict(), a.hidden, a.nblocks, lr=a.lr, weight_decay=a.weight_decay,
                                max_batch=a.batch_size, vloss_weight=a.get("vloss_weight", 1.0),
                                dropout=a.dropout, seed=a.get("seed", 0), amp=self.uses_amp(),
-                               ema_decay=decay, ema_every=every)
+                               ema_decay=decay, ema_every=every, legal_mask=self.mask_on())
             if decay > 0.0 and self._ema_sd is not None:  # (averaged weights loaded before there was a trainer)
                 self._tr.load_ema(self._ema_sd, self.ema_updates)
         return self._tr
@@ -350,7 +366,8 @@ class NNetWrapper:
         table = None
         if sigma > 0.0:
             policies = soft["policies"] if soft else as_device_policies(examples)  # (none: the "visits" error)
-            table = self.yk_net().evaluate(states, targets, values, policies=tuple(policies), per_row=True)["rows"]
+            table = self.yk_net().evaluate(states, targets, values, policies=tuple(policies), per_row=True,
+                                           masked=self.mask_on())["rows"]  # (the surprise of the loss being trained)
         w, _ = K.sample_weights(table, lens, factors, sigma)
         del table
         return K.sample_cdf(w)[0]
@@ -404,7 +421,14 @@ class NNetWrapper:
         in (0, 1) - averaged weights, a departure from the reference: after every
         args.emaEvery-th step (default 1) a device shadow of the parameters moves toward them,
         e <- e + w_t (p - e).  self.nnet stays the raw iterate; after the call yk_net() - predict, the engines,
-        the gate, reanalysis, evaluate, the sampler's surprise - is built from the shadow."""
+        the gate, reanalysis, evaluate, the sampler's surprise - is built from the shadow.
+
+        args.maskIllegal: False (default; the softmax of the policy loss runs over all 3226 actions, as in the
+        reference) or True - the legal-move mask, a departure from the reference: softmax,
+        loss and gradient over each example's valid actions only, which is what the search reads.  The examples
+        must keep its contract - a valid action in every state, valid hard targets, p > 0 on valid actions only -
+        which is checked once per call on the device (K.check_legal; with symmetries on the un-augmented pool:
+        the augmentation keeps targets legal); a violation raises ValueError before any step runs."""
         from . import dist as D
         from .replay import as_device_examples, as_device_policies, check_sample_knobs, sample_rounds
         target = self.args.get("policy_target", "argmax")
@@ -416,10 +440,18 @@ class NNetWrapper:
         T, gamma, sigma = check_sample_knobs(self.args.get("trainSteps", 0) or 0, self.args.get("sampleRecency", 1.0),
                                              self.args.get("sampleSurprise", 0.0))
         ema_on = self.ema_on()  # (bad emaDecay / emaEvery: ValueError, before any device work)
+        mask_on = self.mask_on()  # (a non-bool maskIllegal: ValueError, before any device work)
         tr = self._trainer()
+        if tr.legal_mask != mask_on:  # (the knob changed since the trainer was built)
+            tr.set_legal_mask(mask_on)
         states, targets, values = as_device_examples(examples)
         # "visits": the same rows' policies as a CSR; "argmax" calls the trainer exactly as before
         soft = {"policies": as_device_policies(examples)} if target == "visits" else {}
+        if mask_on and states.shape[0]:  # the mask's contract, once per call, before any step
+            bad, kind = K.check_legal(states, None if soft else targets, soft.get("policies"))
+            if bad >= 0:
+                raise ValueError(f"maskIllegal: example {bad} of the pooled examples breaks the legal-move mask's "
+                                 f"contract: {K.LEGAL_KINDS[kind]}")
         cdf = self._sample_cdf(examples, states, targets, values, soft, gamma, sigma) if T else None
         rounds, key, drawn, picks = sample_rounds(T, self.args.epochs), tr.step_count & 0xFFFFFFFF, 0, None
         pool, aug = (states, targets, soft.get("policies")), None

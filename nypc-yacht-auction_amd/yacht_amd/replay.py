@@ -217,6 +217,17 @@ def check_ema_knobs(emaDecay=0.0, emaEvery=1):
     return decay, int(every)
 
 
+def check_mask_knobs(maskIllegal=False) -> bool:
+    """args.maskIllegal of the legal-move mask as a bool: False / unset - the policy loss is
+    the reference's, a softmax over all 3226 actions - or True - over each example's valid actions only.
+    ValueError for anything that is not a bool (1, "yes" and the like would silently pick a side)."""
+    if maskIllegal is None:
+        return False
+    if not isinstance(maskIllegal, (bool, np.bool_)):
+        raise ValueError(f"maskIllegal must be a bool, got {maskIllegal!r}")
+    return bool(maskIllegal)
+
+
 def sample_rounds(trainSteps: int, epochs: int):
     """The trainSteps sampled steps split over `epochs` rounds: [(first step, one past the last)] per round,
     round e = floor(e T / E) .. floor((e + 1) T / E) - 1; empty rounds (T < E) have first == past."""

@@ -42,11 +42,15 @@ class Trainer:
 
     def __init__(self, state_dict, hidden: int, nblocks: int, lr=2e-3, weight_decay=1e-4, max_batch=512,
                  vloss_weight=1.5, dropout=0.3, seed=0, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=5.0,
-                 amp=False, init_scale=65536.0, growth_interval=2000, ema_decay=0.0, ema_every=1):
+                 amp=False, init_scale=65536.0, growth_interval=2000, ema_decay=0.0, ema_every=1,
+                 legal_mask=False):
         """ema_decay in (0, 1): keep averaged weights on the device - after every
-        ema_every-th apply a shadow of the flat parameters moves toward them (yk_trainer_set_ema); 0: off."""
-        from .replay import check_ema_knobs
+        ema_every-th apply a shadow of the flat parameters moves toward them (yk_trainer_set_ema); 0: off.
+        legal_mask True: the policy softmax, loss and gradient over each example's valid actions only
+        (set_legal_mask); False: over all 3226, the reference's."""
+        from .replay import check_ema_knobs, check_mask_knobs
         ema_decay, ema_every = check_ema_knobs(ema_decay, ema_every)
+        legal_mask = check_mask_knobs(legal_mask)
         self.names = list(state_dict.keys())
         self.shapes = [tuple(t.shape) for t in state_dict.values()]
         arrs = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy()) for t in state_dict.values()]
@@ -64,6 +68,9 @@ class Trainer:
         self._pptr, self._gptr = pp.value, gp.value
         if ema_decay > 0.0:
             self.set_ema(ema_decay, ema_every)
+        self.legal_mask = False
+        if legal_mask:
+            self.set_legal_mask(True)
 
     # ---- device views (no copies)
     def params(self) -> torch.Tensor:
@@ -171,6 +178,17 @@ class Trainer:
         arrs = [np.ascontiguousarray(state_dict[k].detach().to("cpu", torch.float32).numpy()) for k in self.names]
         p = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         call("yk_trainer_set", self.handle, 0, p, -1)
+
+    # ---- legal-move mask
+    def set_legal_mask(self, on: bool):
+        """True: every later backward / step (hard or soft targets) masks each row's invalid actions to -inf
+        where the logits are made - softmax, loss and gradient over the valid actions of states[idx[i]] only, the
+        gradient exactly 0 elsewhere; one more launch per backward.  The examples must keep the contract
+        kernels.check_legal checks.  False: the launches of a trainer that never had the mask."""
+        from .replay import check_mask_knobs
+        on = check_mask_knobs(on)
+        call("yk_trainer_set_legal_mask", self.handle, 1 if on else 0)
+        self.legal_mask = on
 
     # ---- averaged weights (DESIGN.md 7b-ema)
     def set_ema(self, decay: float, every: int = 1):
