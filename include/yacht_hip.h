@@ -431,6 +431,56 @@ int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_re
  * Synchronises `stream`. */
 int yk_fpu_pick(const int64_t* indptr, const float* p, const int32_t* counts, const double* q, const int32_t* ns,
                 int64_t n, double cpuct, double reduction, int32_t* pick, int32_t* unvisited, void* stream);
+/* The two self-play temperatures (AlphaZero / KataGo), a departure from the reference, opt-in; DESIGN.md
+ * section 6h.  Off (the state of a new engine): nothing changes.  Both follow one schedule shape over the
+ * 0-based index m of the real move, in host float64:
+ *   T(m) = final + (early - final) * 2^(-m / halflife)          (early == final: T(m) = final, no halflife needed)
+ * The host builds each table (max_moves doubles, yk_temperature_schedule) and uploads it; the kernels read
+ * T and never evaluate the schedule.
+ * Move-selection temperature (move_early, move_final), on the moves yk_selfplay draws at temp 1 today - real
+ * move m with m + 1 < temp_threshold; the moves from there on stay the argmax path: with T = T(m) and the
+ * recorded visit list n_0 .. n_(k-1) in ascending action order (the pruned list with forced playouts),
+ *   w_i = pow((double)n_i, 1.0 / T), total = the left-to-right sum of w_i, c_i = c_(i-1) + w_i / total,
+ *   last = c_(k-1), u = the game stream's next uniform53, the move = the first i with c_i / last > u
+ * - today's draw with w in place of the counts: one uniform is consumed, so the stream position after the move
+ * does not depend on T.  T == 1.0 exactly runs today's kernel.  info[0] stays 1; T is not recorded.
+ * Root policy temperature (root_early, root_final), where the root noise is or would be applied - every move of
+ * yk_selfplay, with the playout cap its full moves: the root's stored prior over its compact valid set
+ * becomes, in place and once per move, with T = T(m),
+ *   w_j = pow((double)P_j, 1.0 / T), S = sum w_j (float64), P'_j = (float)(w_j / S)
+ * before any UCB scan of that root in the move (the noise's two phases).  With the noise also on, the same
+ * launch then mixes from the rounded P': P''_j = (float)((1 - eps) * (double)P'_j + eps * eta_j), eta
+ * unchanged.  T == 1.0 exactly, or weights that do not sum to > 0, leave P untouched.
+ * Neither is applied by yk_arena, yk_mcts_search or the reanalysis, and neither changes the recorded visit
+ * counts (the policy targets).  The schedules live in the engine, not in yk_engine_config_t.
+ * A pair (early, final) of zeros: that schedule is off.  Otherwise move temperatures outside [0.05, 100] (visit
+ * counts are 16-bit: 65535^20 is finite in float64), root temperatures outside [0.25, 10], a halflife that is
+ * negative, NaN or infinite, or a halflife of 0 while a schedule that is on has early != final: YK_ERR_ARG, the
+ * engine unchanged.  Waits for the device; keeps both tables on the host and on the device. */
+int yk_engine_set_temperatures(yk_engine_t* eng, double move_early, double move_final, double root_early,
+                               double root_final, double halflife);
+/* HOST move_t[max_moves], root_t[max_moves] (either may be NULL): the tables the engine holds; zeros for a
+ * schedule that is off. */
+int yk_engine_temperatures(yk_engine_t* eng, double* move_t, double* root_t);
+/* The schedule itself, the doubles the engine uploads: HOST out[m] = T(m), m = 0 .. n_moves-1, with the host
+ * libm's pow.  NULL out, n_moves < 0, early or final not finite and > 0, halflife negative, NaN or infinite,
+ * or 0 with early != final: YK_ERR_ARG.  Host only. */
+int yk_temperature_schedule(double early, double final_t, double halflife, int n_moves, double* out /* HOST */);
+/* The move draw alone, on n rows given as a CSR: DEVICE indptr[n + 1], counts per entry (a count below 0 is taken
+ * as 0), and per row temps[n] (T) and u[n] (the uniform) -> DEVICE pick[n], the drawn entry's index within its
+ * row (-1: an empty row or counts that are all 0), and total[n], the sum of w.  The same device function as
+ * k_move_end's; one wavefront per row, 64 entries' pow at a time, the sums sequential; no atomics; equal inputs
+ * give equal bits.  A NULL pointer, n < 0, or outputs that alias inputs: YK_ERR_ARG before anything touches the
+ * device.  An indptr that starts below 0 or decreases (or a row of more than 2^31 - 1 entries), or a T that is
+ * not finite and > 0, detected on the device before any row is read: YK_ERR_RANGE, the outputs untouched.
+ * Synchronises `stream`. */
+int yk_temperature_pick(const int64_t* indptr, const int32_t* counts, const double* temps, const double* u, int64_t n,
+                        int32_t* pick, double* total, void* stream);
+/* The root prior transform alone, on n rows: DEVICE p[n][3226], row i compact over its first nvalid[i] entries
+ * (clamped to 0 .. 3226), temps[n] -> DEVICE out[n][3226], P' over those entries and 0 past them.  The same
+ * device function as the engine's, so the same bits.  A NULL pointer, n < 0 or out == p: YK_ERR_ARG; a T that
+ * is not finite and > 0: YK_ERR_RANGE, out untouched.  Synchronises `stream`. */
+int yk_root_temper(const float* p, const int32_t* nvalid, const double* temps, int n, float* out, void* stream);
 /* Per-kernel timing with HIP events on the engine's stream; resets the accumulators.
  * enable = 0 off, k > 0 on: the per-move launches are timed every time, the per-simulation
  * forward / expand pair in every k-th simulation of a move (1 = all; an event record between
@@ -438,8 +488,8 @@ int yk_fpu_pick(const int64_t* indptr, const float* p, const int32_t* counts, co
  * yk_engine_kernel_times (launches counts the timed ones): HOST ms[8],
  * launches[8] for classes 0 first descent of a move, 1 forward (the whole predict), 2 unused,
  * 3 expand + backup + the next descent, 4 move begin (root / tree compaction), 5 move end
- * (policy, sampling, real step), 6 the root noise (both launches of a move; 0 launches when the noise
- * is off - with it on and full root scans, simulation 1's descent is its own launch, timed as class 2),
+ * (policy, sampling, real step), 6 the root noise and the root policy temperature, which share their launches
+ * (both launches of a move; 0 launches when both are off - with one on and full root scans, simulation 1's descent is its own launch, timed as class 2),
  * 7 the root value (one launch per move after the move end; 0 launches without record_root_values). */
 int yk_engine_profile(yk_engine_t* eng, int enable);
 int yk_engine_kernel_times(yk_engine_t* eng, double* ms, int64_t* launches);
@@ -484,7 +534,10 @@ int yk_engine_predictions(yk_engine_t* eng, float* pi, float* v, yk_state_t* lea
 /* Root noise of the last yk_selfplay, for the R record_predictions games: HOST before[R][max_moves][3226],
  * after[R][max_moves][3226] (either may be NULL), dense by action - the prior P of move m's root as the
  * noise found it and P' as it left it, 0 at invalid actions and for moves >= the game's n_moves.
- * YK_ERR_STATE unless the engine has both record_predictions and noise on and has played a batch. */
+ * With the root policy temperature on (yk_engine_set_temperatures) `before` is the prior before the tempering
+ * and `after` what the search scans: the tempered prior, or with the noise also on its mix.
+ * YK_ERR_STATE unless the engine has record_predictions and the noise or the root policy temperature on and has
+ * played a batch. */
 int yk_engine_root_priors(yk_engine_t* eng, float* before, float* after);
 /* test: HOST p[3226] = the prior P stored in the tree for the root of game `game`'s current move (tree
  * `game`), dense by action, 0 at invalid actions: what the expansion wrote (MCTS.py:90-107) and the UCB scans

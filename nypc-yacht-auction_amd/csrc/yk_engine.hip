@@ -28,6 +28,7 @@
 #include "yk_forced.h"
 #include "yk_fpu.h"
 #include "yk_net.h"
+#include "yk_temper.h"
 
 #define YK_MAX_GROUPS 8
 
@@ -1498,11 +1499,22 @@ __global__ __launch_bounds__(256) void k_root_sort(EngDev d) {
 // kind: 0, or YK_REC_FAST for a fast move of the playout cap (ORed into the record's status word).
 // PRUNE (a full self-play move with forced playouts and pruning on): the gathered list is
 // pruned in LDS before it is recorded and drawn from - the tree keeps its raw N and Q, info[4] the raw Ns.
-template <bool PRUNE, class... FD>  // (FD: as k_select)
+// TEMPER (a move the move-selection temperature applies to, DESIGN.md s6h: a temp-1 move of self-play whose
+// T is not 1): the move is drawn from N^(1/T) over the same list, by the whole wave (wave_temper_pick,
+// yk_temper.h), with the one uniform the temp-1 draw takes; everything else, the record included, is as without.
+__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd, const TemperDev&) { return fd; }
+__device__ __forceinline__ ForcedDev forced_arg(const TemperDev&) { return ForcedDev{0.0, 0.0}; }
+__device__ __forceinline__ TemperDev temper_arg() { return TemperDev{nullptr, nullptr}; }
+__device__ __forceinline__ TemperDev temper_arg(const ForcedDev&) { return TemperDev{nullptr, nullptr}; }
+__device__ __forceinline__ const TemperDev& temper_arg(const TemperDev& td) { return td; }
+__device__ __forceinline__ const TemperDev& temper_arg(const ForcedDev&, const TemperDev& td) { return td; }
+template <bool PRUNE, bool TEMPER, class... FD>  // (FD: as k_select)
 __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, FD... fdp) {
-    static_assert(sizeof...(FD) == (PRUNE ? 1 : 0), "ForcedDev with PRUNE, else no further argument");
+    static_assert(sizeof...(FD) == (PRUNE ? 1 : 0) + (TEMPER ? 1 : 0),
+                  "ForcedDev with PRUNE, TemperDev with TEMPER, no further argument");
     const ForcedDev fd = forced_arg(fdp...);
     __shared__ uint32_t vis_all[GAMES_PER_BLOCK][ASIZE];
+    __shared__ double stage_all[TEMPER ? GAMES_PER_BLOCK : 1][TEMPER ? 64 : 1];  // wave_temper_pick's pieces of 64 terms
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int e = d.e_lo + blockIdx.x * GAMES_PER_BLOCK + w;
     if (e >= d.e_hi) return;
@@ -1610,6 +1622,18 @@ __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, 
     const bool room = voff + nvis <= d.VCAP;
     if (room)
         for (int i = lane; i < nvis; i += 64) d.rec_visits[vbase + voff + i] = vis[i];
+    // the tempered draw needs the whole wave; every lane takes the same uniform from its own copy of the
+    // stream, and lane 0 below advances the game's by that one draw
+    int tpick = -1;
+    double ttotal = 0.0;
+    if constexpr (TEMPER) {
+        if (!idle && !d.arena && move + 1 < d.temp_threshold) {  // (wave-uniform) a temp-1 move, as below
+            Stream ru{d.seed, d.env_id[e], d.ctr[e]};
+            const double u = ru.uniform53();
+            tpick = wave_temper_pick([&](int i) { return vis[i] & 0xFFFF; }, nvis, 1.0 / temper_arg(fdp...).move_t[move],
+                                     u, stage_all[w], lane, &ttotal);
+        }
+    }
     if (lane != 0) return;
     if (!room) atomicOr(d.err, ERR_VISITS);
     d.rec_voff[(long)e * (d.M + 1) + move + 1] = room ? voff + nvis : voff;
@@ -1644,6 +1668,14 @@ __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, 
         // np.random.choice(len(pi), p=one-hot) still draws in Coach (Coach.py:65); the Arena
         // agent is np.argmax(pi) (Coach.py:124-125), which does not
         if (!d.arena) (void)rs.uniform53();
+    } else if (TEMPER) {
+        // the wave drew above from N^(1/T): the same single uniform, the same error when there is nothing to draw from
+        if (!(ttotal > 0.0)) {
+            atomicOr(d.err, ERR_ZERO_COUNTS);
+        } else {
+            (void)rs.uniform53();
+            action = tpick >= 0 ? (int)(vis[tpick] >> 16) : ASIZE;
+        }
     } else {
         // probs = counts / sum; np.random.choice(len(pi), p=probs): cumsum, /= cdf[-1],
         // searchsorted(u, 'right')
@@ -1805,6 +1837,12 @@ struct yk_engine {
     bool forced_prune = true;    // of full moves, and whether k_move_end prunes the move's counts
     bool fpu_on = false;         // first-play urgency (yk_engine_set_fpu) in every search of this
     double fpu_r = 0.0, fpu_r_root = 0.0;  // engine: the reduction at interior nodes and at depth 0
+    // the self-play temperatures (yk_engine_set_temperatures): each schedule's T by move, M
+    // entries, on the host (which picks each move's instantiation from it) and on the device (which reads T)
+    bool move_temp = false, root_temp = false;
+    std::vector<double> move_t, root_t;
+    TemperDev td{nullptr, nullptr};
+    double *dev_move_t = nullptr, *dev_root_t = nullptr;
     yk_engine() = default;
     yk_engine(const yk_engine&) = delete;
     yk_engine& operator=(const yk_engine&) = delete;
@@ -1899,8 +1937,12 @@ int check_errors(yk_engine* eng, hipStream_t s) {
 // forced (a full self-play move with forced playouts): the descents are the FORCED
 // instantiations; every other caller runs the unforced ones, whose code the feature leaves as it was.
 // Whether they are the FPU ones is the engine's state (yk_engine_set_fpu), the same for every caller.
+// root_t (a self-play move under the root policy temperature, DESIGN.md s6h: the device table of T by move):
+// the two launches of noise_move are the tempered forms of k_root_noise - with `with_noise` the one that also
+// mixes the noise, else the one without the sampler.  NULL: the launches are the noise's own, as before.
 int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint32_t* env_ids, uint64_t* ctr,
-             int noise_move = -1, const ForcedDev* forced = nullptr) {
+             int noise_move = -1, const ForcedDev* forced = nullptr, const double* root_t = nullptr,
+             bool with_noise = true) {
     const dim3 bb(256);
     if (sims <= 0) return YK_OK;
     // first-play urgency: every search of an engine it is set on runs the FPU instantiations
@@ -1928,12 +1970,17 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
         else
             hipLaunchKernelGGL((k_expand_backup<false, false>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr);
     };
+    const auto root_noise = [&](const EngDev& dd, hipStream_t s, int phase) {
+        return root_t ? yk_launch_root_temper(&dd, sizeof(dd), &eng->nz, sizeof(eng->nz), root_t, with_noise ? 1 : 0,
+                                              noise_move, phase, s)
+                      : yk_launch_root_noise(&dd, sizeof(dd), &eng->nz, sizeof(eng->nz), noise_move, phase, s);
+    };
     EngDev dg[YK_MAX_GROUPS];
     for (int g = 0; g < G; g++) {
         dg[g] = G == 1 ? eng->d : group_dev(eng, g);
         if (noise_move >= 0) {  // the roots already in the tree
             prof_mark(eng, g, KC_NOISE, st[g]);
-            const int rc = yk_launch_root_noise(&dg[g], sizeof(dg[g]), &eng->nz, sizeof(eng->nz), noise_move, 0, st[g]);
+            const int rc = root_noise(dg[g], st[g], 0);
             if (rc) return rc;
         }
         prof_mark(eng, g, KC_SELECT, st[g]);  // the first descent; later ones run in k_expand_backup's tail
@@ -1982,7 +2029,7 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
             }
             if (noise) {
                 prof_mark(eng, g, KC_NOISE, st[g]);  // (simulation 0 is always a timed one)
-                const int rc = yk_launch_root_noise(&d, sizeof(d), &eng->nz, sizeof(eng->nz), noise_move, 1, st[g]);
+                const int rc = root_noise(d, st[g], 1);
                 if (rc) return rc;
                 if (!sort_root && k + 1 < sims) {  // the second descent on its own, as after k_root_sort
                     prof_mark(eng, g, KC_SCAN, st[g]);
@@ -2245,7 +2292,11 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
     const ForcedDev fd{eng->forced_k, eng->cfg.cpuct};
     if (root_values)  // info[..][7] = 0 also past a game's end: a zero word is "no value recorded"
         YK_HIP(hipMemsetAsync(d.rec_info, 0, sizeof(int32_t) * (size_t)d.E * d.M * 8, s));
-    if (noise && eng->nz.prior_after) {  // dense by action: 0 off the valid set and past the game's end
+    // the self-play temperatures: never in the arenas; the root's where the noise is or would be
+    const bool root_temp = eng->root_temp && !d.arena;
+    const bool move_temp = eng->move_temp && !d.arena;
+    const bool root_edit = noise || root_temp;  // the two launches of k_root_noise per full move
+    if (root_edit && eng->nz.prior_after) {  // dense by action: 0 off the valid set and past the game's end
         const size_t nb = sizeof(float) * (((size_t)d.E + d.rec_stride - 1) / d.rec_stride) * (size_t)d.M * ASIZE;
         YK_HIP(hipMemsetAsync(eng->nz.prior_before, 0, nb, s));
         YK_HIP(hipMemsetAsync(eng->nz.prior_after, 0, nb, s));
@@ -2267,16 +2318,25 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
         const bool fast = capped && !playout_full(seed, env_base, move, eng->full_prob);
         eng->fast_moves += fast;
         if (!d.arena || d.arena_agent == YK_PLAYER_MCTS || d.arena_opp == YK_PLAYER_MCTS) {
-            int rc = run_sims(eng, G, st, fast ? eng->fast_sims : d.sims, d.env_id, d.ctr, noise && !fast ? move : -1,
-                              forcing && !fast ? &fd : nullptr);
+            int rc = run_sims(eng, G, st, fast ? eng->fast_sims : d.sims, d.env_id, d.ctr, root_edit && !fast ? move : -1,
+                              forcing && !fast ? &fd : nullptr, root_temp ? eng->td.root_t : nullptr, noise);
             if (rc) return rc;
         }
+        // the tempered draw: a temp-1 move (k_move_end's own test) whose T is not exactly 1
+        const bool temper = move_temp && move + 1 < d.temp_threshold && eng->move_t[move] != 1.0;
         for (int g = 0; g < G; g++) {
             prof_mark(eng, g, KC_MOVE_END, st[g]);
-            if (forcing && !fast && eng->forced_prune)
-                hipLaunchKernelGGL((k_move_end<true, ForcedDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move, 0, fd);
+            const bool prune = forcing && !fast && eng->forced_prune;
+            if (prune && temper)
+                hipLaunchKernelGGL((k_move_end<true, true, ForcedDev, TemperDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
+                                   0, fd, eng->td);
+            else if (prune)
+                hipLaunchKernelGGL((k_move_end<true, false, ForcedDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move, 0, fd);
+            else if (temper)
+                hipLaunchKernelGGL((k_move_end<false, true, TemperDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
+                                   fast ? YK_REC_FAST : 0, eng->td);
             else
-                hipLaunchKernelGGL((k_move_end<false>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
+                hipLaunchKernelGGL((k_move_end<false, false>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
                                    fast ? YK_REC_FAST : 0);
             YK_LAUNCHED();
             if (root_values) {  // the games with nmoves == move + 1; root[e] is still this move's root
@@ -2301,7 +2361,7 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)(((long)d.E * d.M + 255) / 256)), dim3(256), 0, s, d);
     YK_LAUNCHED();
     eng->have_records = true;
-    eng->have_priors = noise && eng->nz.prior_after;
+    eng->have_priors = root_edit && eng->nz.prior_after;
     return check_errors(eng, s);
 }
 }  // namespace
@@ -2338,6 +2398,56 @@ int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_re
     eng->fpu_on = on != 0;
     eng->fpu_r = reduction;
     eng->fpu_r_root = root_reduction;
+    return YK_OK;
+}
+
+int yk_engine_set_temperatures(yk_engine_t* eng, double move_early, double move_final, double root_early,
+                               double root_final, double halflife) {
+    if (!eng) return YK_ERR_ARG;
+    // a pair of zeros: that schedule is off; else both of its ends within the range (a NaN fails the comparisons)
+    const auto pair_ok = [](double a, double b, double lo, double hi) {
+        return (a == 0.0 && b == 0.0) || (a >= lo && a <= hi && b >= lo && b <= hi);
+    };
+    if (!pair_ok(move_early, move_final, 0.05, 100.0) || !pair_ok(root_early, root_final, 0.25, 10.0)) return YK_ERR_ARG;
+    if (!(halflife >= 0.0) || std::isinf(halflife)) return YK_ERR_ARG;
+    const bool mv = move_final != 0.0, rt = root_final != 0.0;
+    if (halflife == 0.0 && ((mv && move_early != move_final) || (rt && root_early != root_final))) return YK_ERR_ARG;
+    EngDev& d = eng->d;
+    const size_t M = (size_t)d.M, E = (size_t)d.E;
+    std::vector<double> mt(M), rtab(M);
+    if (mv) YK_TRY(yk_temperature_schedule(move_early, move_final, halflife, d.M, mt.data()));
+    if (rt) YK_TRY(yk_temperature_schedule(root_early, root_final, halflife, d.M, rtab.data()));
+    YK_HIP(hipDeviceSynchronize());  // (no batch of this engine is in flight while its tables change)
+    if (mv) {
+        if (!eng->dev_move_t) YK_TRY(eng->mem.alloc(&eng->dev_move_t, M));
+        YK_HIP(hipMemcpy(eng->dev_move_t, mt.data(), sizeof(double) * M, hipMemcpyHostToDevice));
+    }
+    if (rt) {
+        if (!eng->dev_root_t) YK_TRY(eng->mem.alloc(&eng->dev_root_t, M));
+        YK_HIP(hipMemcpy(eng->dev_root_t, rtab.data(), sizeof(double) * M, hipMemcpyHostToDevice));
+        // what the root noise allocates when it is configured: the per-game byte and the prior records
+        if (!eng->nz.noised) YK_TRY(eng->mem.alloc(&eng->nz.noised, E));
+        if (d.rec_pred && !eng->nz.prior_after) {
+            const size_t R = (E + d.rec_stride - 1) / d.rec_stride;
+            YK_TRY(eng->mem.alloc(&eng->nz.prior_before, R * M * ASIZE));
+            YK_TRY(eng->mem.alloc(&eng->nz.prior_after, R * M * ASIZE));
+        }
+    }
+    eng->move_temp = mv;
+    eng->root_temp = rt;
+    eng->move_t = mv ? mt : std::vector<double>();
+    eng->root_t = rt ? rtab : std::vector<double>();
+    eng->td = TemperDev{mv ? eng->dev_move_t : nullptr, rt ? eng->dev_root_t : nullptr};
+    return YK_OK;
+}
+
+int yk_engine_temperatures(yk_engine_t* eng, double* move_t, double* root_t) {
+    if (!eng) return YK_ERR_ARG;
+    // HOST [max_moves] each; a schedule that is off reads as zeros
+    for (int m = 0; m < eng->d.M; m++) {
+        if (move_t) move_t[m] = eng->move_temp ? eng->move_t[m] : 0.0;
+        if (root_t) root_t[m] = eng->root_temp ? eng->root_t[m] : 0.0;
+    }
     return YK_OK;
 }
 

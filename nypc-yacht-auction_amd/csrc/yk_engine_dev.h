@@ -149,7 +149,7 @@ struct EngDev {
 // the argument layout of every other kernel, is the same with and without the feature.
 struct NoiseDev {
     double alpha, eps;
-    uint8_t* noised;      // [E] 1 once the move's root was noised (phase 0), so phase 1 passes it by
+    uint8_t* noised;      // [E] 1 once the move's root was noised or tempered (phase 0), so phase 1 passes it by
     float* prior_before;  // [R][M][3226] record_predictions: the root's P, dense by action, before the mix
     float* prior_after;   // [R][M][3226] and after it (NULL: not recorded)
 };
@@ -298,6 +298,13 @@ static_assert(std::is_trivially_copyable<EngDev>::value && std::is_trivially_cop
 __attribute__((visibility("hidden"))) int yk_launch_root_noise(const void* engdev, size_t engdev_bytes,
                                                                const void* noisedev, size_t noisedev_bytes, int move,
                                                                int phase, hipStream_t stream);
+// yk_noise.hip: the same launch with the root policy temperature - `root_t` the DEVICE table of T
+// by move (M entries) - and, with_noise, the noise mixed from the tempered prior in the same kernel; without
+// it the form that has no sampler.  `noisedev` carries the per-game byte and the prior records either way.
+__attribute__((visibility("hidden"))) int yk_launch_root_temper(const void* engdev, size_t engdev_bytes,
+                                                                const void* noisedev, size_t noisedev_bytes,
+                                                                const double* root_t, int with_noise, int move,
+                                                                int phase, hipStream_t stream);
 // yk_rootval.hip: launches k_root_value for the games [e_lo, e_hi) of `engdev` after k_move_end(rvdev.move),
 // on the same terms.
 __attribute__((visibility("hidden"))) int yk_launch_root_value(const void* engdev, size_t engdev_bytes,

@@ -1,10 +1,13 @@
 // yk_noise.hip - Dirichlet root noise of self-play: the kernel that mixes eta ~ Dir(alpha)
 // into each real move's root prior, and the standalone sampler entry point.  Both run block_dirichlet
 // (yk_noise.h), so the noise a search sees and the noise yk_dirichlet_noise returns are the same bits.
+// The same kernel, as a template, also applies the root policy temperature (yk_temper.h): the
+// root's prior is edited in one place, at most once per move.
 #include <string.h>
 
 #include "yk_engine_dev.h"
 #include "yk_noise.h"
+#include "yk_temper.h"
 
 namespace {
 
@@ -20,9 +23,20 @@ namespace {
 // A root with Ns = 0 has had no scan yet: its summary first_j is recomputed from P' with the scan's
 // own f32 operations (the expansion's, lowest index among equals).  k_root_sort runs after phase 1,
 // so the root's order is P''s.
-__global__ __launch_bounds__(NOISE_THREADS) void k_root_noise(EngDev d, NoiseDev nz, int move, int phase) {
-    __shared__ double eta[ASIZE];
+// TEMPER (the root policy temperature; its argument is the table of T by move): P is first
+// replaced by f32(P^(1/T) / S) over the same compact set (block_temper_weights, yk_temper.h: P read from
+// memory once, the weights staged in LDS), and the noise then mixes from that rounded value - one launch
+// does both.  NOISE = false is the tempering alone, without the sampler.  T == 1.0 exactly, or a prior
+// whose weights do not sum to > 0, leaves P as it is.  <false, true> is the kernel the noise alone runs.
+__device__ __forceinline__ const double* temper_table(const double* root_t) { return root_t; }
+template <bool TEMPER, bool NOISE, class... TD>
+__global__ __launch_bounds__(NOISE_THREADS) void k_root_noise(EngDev d, NoiseDev nz, int move, int phase, TD... root_t) {
+    static_assert(sizeof...(TD) == (TEMPER ? 1 : 0) && (TEMPER || NOISE), "the table of T with TEMPER, else no further argument");
+    static_assert(TEMPER_THREADS == NOISE_THREADS, "one workgroup shape");
+    __shared__ double eta[NOISE ? ASIZE : 1];
     __shared__ double wsum[4];
+    __shared__ double tw[TEMPER ? ASIZE : 1];
+    __shared__ double tsum[4];
     __shared__ int s_nid;
     __shared__ float s_fb[NOISE_THREADS / 64];
     __shared__ int s_fj[NOISE_THREADS / 64];
@@ -46,21 +60,33 @@ __global__ __launch_bounds__(NOISE_THREADS) void k_root_noise(EngDev d, NoiseDev
     if (V <= 0 || V > ASIZE) return;
     const uint32_t Ns = nd.Ns;
     float* P = d.arenaP + (long)t * d.AE + nd.p_off;
-    block_dirichlet(d.seed, d.env_id[e], (uint32_t)move, V, nz.alpha, eta, wsum);
+    if constexpr (NOISE) block_dirichlet(d.seed, d.env_id[e], (uint32_t)move, V, nz.alpha, eta, wsum);
     const bool rec = nz.prior_after && d.rec_pred && (e % d.rec_stride) == 0 && move < d.M;
     const long rslot = rec ? ((long)(e / d.rec_stride) * d.M + move) * ASIZE : 0;
     const VInfo vi = unpack_vinfo(nd.vinfo, (uint32_t)V);
     const double keep = 1.0 - nz.eps;
     const float sqe0 = (float)sqrt((double)0u + 1e-8);
+    bool tempered = false;  // (block-uniform)
+    double S = 0.0;
+    if constexpr (TEMPER) {
+        const double T = temper_table(root_t...)[move];
+        if (T != 1.0) {
+            S = block_temper_weights(P, V, 1.0 / T, tw, tsum, [&](int j, float p) {
+                if (rec) nz.prior_before[rslot + compact_to_action(vi, j)] = p;
+            });
+            tempered = S > 0.0;
+        }
+    }
     float fb = -INFINITY;
     int fj = 0x7FFFFFFF;
     for (int j = tid; j < V; j += NOISE_THREADS) {
-        const float p = P[j];
-        const float q = (float)(keep * (double)p + nz.eps * eta[j]);
-        P[j] = q;
+        const float p = (TEMPER && tempered) ? tempered_prior(tw[j], S) : P[j];
+        float q = p;
+        if constexpr (NOISE) q = (float)(keep * (double)p + nz.eps * eta[j]);
+        if (NOISE || tempered) P[j] = q;
         if (rec) {
             const int a = compact_to_action(vi, j);
-            nz.prior_before[rslot + a] = p;
+            if (!(TEMPER && tempered)) nz.prior_before[rslot + a] = p;  // (tempered: the first pass recorded it)
             nz.prior_after[rslot + a] = q;
         }
         const float u0 = (d.c32 * q) * sqe0;
@@ -111,8 +137,27 @@ int yk_launch_root_noise(const void* engdev, size_t engdev_bytes, const void* no
     memcpy(&d, engdev, sizeof(d));
     memcpy(&nz, noisedev, sizeof(nz));
     if (d.e_hi <= d.e_lo) return YK_OK;
-    hipLaunchKernelGGL(k_root_noise, dim3((unsigned)(d.e_hi - d.e_lo)), dim3(NOISE_THREADS), 0, stream, d, nz, move,
-                       phase);
+    hipLaunchKernelGGL((k_root_noise<false, true>), dim3((unsigned)(d.e_hi - d.e_lo)), dim3(NOISE_THREADS), 0, stream, d,
+                       nz, move, phase);
+    YK_LAUNCHED();
+    return YK_OK;
+}
+
+int yk_launch_root_temper(const void* engdev, size_t engdev_bytes, const void* noisedev, size_t noisedev_bytes,
+                          const double* root_t, int with_noise, int move, int phase, hipStream_t stream) {
+    if (!engdev || !noisedev || !root_t || engdev_bytes != sizeof(EngDev) || noisedev_bytes != sizeof(NoiseDev))
+        return YK_ERR_ARG;
+    EngDev d;
+    NoiseDev nz;
+    memcpy(&d, engdev, sizeof(d));
+    memcpy(&nz, noisedev, sizeof(nz));
+    if (move < 0 || move >= d.M) return YK_ERR_ARG;  // the table has M entries
+    if (d.e_hi <= d.e_lo) return YK_OK;
+    const dim3 grid((unsigned)(d.e_hi - d.e_lo)), block(NOISE_THREADS);
+    if (with_noise)
+        hipLaunchKernelGGL((k_root_noise<true, true, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
+    else
+        hipLaunchKernelGGL((k_root_noise<true, false, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
     YK_LAUNCHED();
     return YK_OK;
 }

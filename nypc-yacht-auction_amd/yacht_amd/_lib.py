@@ -137,6 +137,11 @@ SIGNATURES = {
     "yk_policy_prune": [P, P, P, P, P, P, C.c_int64, C.c_double, C.c_double, P, P],
     "yk_engine_set_fpu": [P, I, C.c_double, C.c_double],
     "yk_fpu_pick": [P, P, P, P, P, C.c_int64, C.c_double, C.c_double, P, P, P],
+    "yk_engine_set_temperatures": [P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double],
+    "yk_engine_temperatures": [P, P, P],
+    "yk_temperature_schedule": [C.c_double, C.c_double, C.c_double, I, P],
+    "yk_temperature_pick": [P, P, P, P, C.c_int64, P, P, P],
+    "yk_root_temper": [P, P, P, I, P, P],
     "yk_ema_weight": [C.c_double, C.c_int64, P],
     "yk_ema_update": [P, P, C.c_int64, C.c_float, P],
     "yk_trainer_set_ema": [P, C.c_double, I],
@@ -154,8 +159,8 @@ _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_re
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
 # search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap, the
-# averaged weights, the forced playouts, the first-play urgency and the legal-move mask (A/B baselines may
-# predate them)
+# averaged weights, the forced playouts, the first-play urgency, the legal-move mask and the self-play
+# temperatures (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
@@ -164,7 +169,9 @@ _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk
           "yk_policies_take", "yk_ema_weight", "yk_ema_update", "yk_trainer_set_ema", "yk_trainer_ema_buffer",
           "yk_trainer_ema_get", "yk_trainer_ema_set", "yk_trainer_ema_state", "yk_engine_set_forced_playouts",
           "yk_policy_prune", "yk_engine_set_fpu", "yk_fpu_pick", "yk_trainer_set_legal_mask",
-          "yk_examples_check_legal", "yk_examples_metrics_legal", "yk_net_evaluate_legal"}
+          "yk_examples_check_legal", "yk_examples_metrics_legal", "yk_net_evaluate_legal",
+          "yk_engine_set_temperatures", "yk_engine_temperatures", "yk_temperature_schedule", "yk_temperature_pick",
+          "yk_root_temper"}
 _lib = None
 
 

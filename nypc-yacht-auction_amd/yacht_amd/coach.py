@@ -25,6 +25,10 @@ any number of ranks (one process per GPU, torch.distributed):
 * first-play urgency (opt-in, ``args.fpuReduction``, ``fpuRootReduction``; not in the reference):
   an unvisited edge starts from the visited children's visit-weighted mean less a reduction, not from 0 - in
   everything that searches: self-play, the held-out games, the reanalysis, the gate, ``MCTSArena``, the plugin.
+* self-play temperatures (opt-in, ``args.moveTemperature`` / ``moveTemperatureEarly``,
+  ``rootPolicyTemperature`` / ``rootPolicyTemperatureEarly``, ``temperatureHalflife``; not in the reference;
+  DESIGN.md 6h): a temp-1 move is drawn from N^(1/T) and the self-play root searched with P^(1/T) renormalised,
+  T on a schedule over the game - in self-play and the held-out games only; the policy targets are untouched.
 * held-out evaluation (opt-in, ``args.holdoutEps = m``; not in the reference): m more self-play games per
   iteration that never enter training, on which the previous and the new net are evaluated after
   train (``NNetWrapper.evaluate``; ``last_eval``, ``eval_history``).  The gate does not use it.
@@ -111,6 +115,9 @@ class Coach:
         from .replay import check_fpu_knobs
         self.fpu_reduction, self.fpu_root_reduction = check_fpu_knobs(args.get("fpuReduction", None),
                                                                       args.get("fpuRootReduction", None))
+        # the self-play temperatures: self-play and the held-out games only.  Unset: off
+        from .replay import temperature_knobs_of
+        self.temperature_knobs = temperature_knobs_of(args)
         # averaged weights: NNetWrapper's knobs, checked here as well.  With emaDecay set the
         # net that plays, gates and reanalyses is the averaged one (NNetWrapper.yk_net); learn's flow is unchanged
         from .replay import check_ema_knobs
@@ -161,7 +168,9 @@ class Coach:
                               # forced playouts and pruning; again the same for the held-out games
                               forced_playouts_k=self.forced_k, forced_prune=self.forced_prune,
                               # first-play urgency; the same for the held-out games
-                              fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction)
+                              fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction,
+                              # the move-selection and root policy temperatures; the same for the held-out games
+                              **self.temperature_knobs)
 
     def _value_targets_on(self) -> bool:
         return (self.value_mix, self.value_lambda) != (0.0, 1.0)

@@ -25,7 +25,8 @@ class SelfPlayEngine:
                  dual_trees: bool = False, opponent_net=None, dirichlet_alpha: float = 0.0,
                  dirichlet_eps: float = 0.0, record_root_values: bool = False, playout_fast_sims: int = 0,
                  playout_full_prob: float = 1.0, forced_playouts_k: float = 0.0, forced_prune: bool = True,
-                 fpu_reduction=None, fpu_root_reduction=None):
+                 fpu_reduction=None, fpu_root_reduction=None, move_temperature=None, move_temperature_early=None,
+                 root_policy_temperature=None, root_policy_temperature_early=None, temperature_halflife=None):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -82,6 +83,25 @@ class SelfPlayEngine:
             except Exception:
                 self.close()
                 raise
+        # the self-play temperatures in run() (never in arena()), each on the schedule T(m) = final +
+        # (early - final) * 2 ** (-m / temperature_halflife) over the real move m: move_temperature draws a temp-1
+        # move from N ** (1 / T) (temp_threshold still decides where argmax begins), root_policy_temperature
+        # searches the root with P ** (1 / T) renormalised, applied before the Dirichlet mix.  None is off
+        try:
+            from .replay import check_temperature_knobs
+            tk = check_temperature_knobs(move_temperature, move_temperature_early, root_policy_temperature,
+                                         root_policy_temperature_early, temperature_halflife)
+            self.move_temperature, self.move_temperature_early = tk["move_temperature"], tk["move_temperature_early"]
+            self.root_policy_temperature = tk["root_policy_temperature"]
+            self.root_policy_temperature_early = tk["root_policy_temperature_early"]
+            self.temperature_halflife = tk["temperature_halflife"]
+            if self.move_temperature is not None or self.root_policy_temperature is not None:
+                call("yk_engine_set_temperatures", self.handle, self.move_temperature_early or 0.0,
+                     self.move_temperature or 0.0, self.root_policy_temperature_early or 0.0,
+                     self.root_policy_temperature or 0.0, self.temperature_halflife or 0.0)
+        except Exception:
+            self.close()
+            raise
         self.opponent_net = opponent_net
         if opponent_net is not None:
             # MCTS vs MCTS with two nets, each seat its own tree (the gating arena, Coach.py:117-139)
@@ -143,6 +163,8 @@ class SelfPlayEngine:
         kt = {k: (float(ms[i]), int(n[i])) for i, k in enumerate(self.KERNEL_CLASSES) if k != "unused"}
         if self.cfg.dirichlet_alpha > 0 and self.cfg.dirichlet_eps > 0:
             kt["root_noise"] = (float(ms[6]), int(n[6]))  # k_root_noise, two launches per move (class 6)
+        if self.root_policy_temperature is not None:  # its tempered form: with the noise on, the same launches
+            kt["root_temper"] = (float(ms[6]), int(n[6]))
         if self.cfg.record_root_values:
             kt["root_value"] = (float(ms[7]), int(n[7]))  # k_root_value, one launch per move (class 7)
         return kt
@@ -217,6 +239,15 @@ class SelfPlayEngine:
         after = np.zeros_like(before)
         call("yk_engine_root_priors", self.handle, before.ctypes.data, after.ctypes.data)
         return before, after
+
+    def temperatures(self):
+        """(move_t, root_t), float64[max_moves] each: the tables of T by real move this engine holds (DESIGN.md
+        6h), None for a schedule that is off."""
+        mt = np.zeros(self.max_moves, dtype=np.float64)
+        rt = np.zeros(self.max_moves, dtype=np.float64)
+        call("yk_engine_temperatures", self.handle, mt.ctypes.data, rt.ctypes.data)
+        return (mt if self.move_temperature is not None else None,
+                rt if self.root_policy_temperature is not None else None)
 
     def record_bytes(self) -> int:
         n = int(lib().yk_engine_record_bytes(self.handle))

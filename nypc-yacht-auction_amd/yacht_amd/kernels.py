@@ -504,11 +504,73 @@ def fpu_pick(indptr, p, counts, q, ns, cpuct: float, reduction: float, stream=No
     return pick[:n], unv[:n]
 
 
+# ---------------------------------------------------------------- self-play temperatures
+def temperature_schedule(early: float, final: float, halflife, n_moves: int):
+    """yk_temperature_schedule: float64[n_moves], T(m) = final + (early - final) * 2 ** (-m / halflife) - the table
+    an engine uploads, bit for bit the Python expression (early == final needs no halflife).  Host only."""
+    out = np.zeros(max(int(n_moves), 1), dtype=np.float64)
+    call("yk_temperature_schedule", float(early), float(final), float(halflife or 0.0), int(n_moves), out.ctypes.data)
+    return out[:int(n_moves)]
+
+
+def temperature_pick(indptr, counts, temps, u, stream=None):
+    """The move draw from N ** (1 / T) on rows of visit counts given as a CSR (yk_temperature_pick), the device
+    function k_move_end runs: device tensors indptr int64 [n + 1], counts int32 per entry, and per row temps
+    float64 (T) and u float64 (the uniform).  Returns (pick, total): device int32 [n], the drawn entry's index
+    within its row (-1: nothing to draw from), and float64 [n], the sum of the weights.  ValueError for row
+    pointers that start below 0, decrease or reach past counts, or a T that is not finite and > 0.
+    Synchronises."""
+    want = ((indptr, torch.int64), (counts, torch.int32), (temps, torch.float64), (u, torch.float64))
+    for t, dt in want:
+        if t.dtype != dt or t.dim() != 1:
+            raise TypeError("temperature_pick takes vectors: indptr int64, counts int32, temps / u float64")
+    n = int(indptr.numel()) - 1
+    if n < 0 or int(temps.numel()) != n or int(u.numel()) != n:
+        raise ValueError("temperature_pick: indptr has n + 1 entries, temps and u n")
+    if int(indptr[-1]) > int(counts.numel()):
+        raise ValueError("temperature_pick: indptr reaches past counts")
+    pick = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    total = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
+    spare = torch.empty(2, dtype=torch.int64, device="cuda")
+    a = [ptr(t) or ptr(spare) for t in (counts, temps, u)]
+    try:
+        call("yk_temperature_pick", ptr(indptr), a[0], a[1], a[2], n, ptr(pick), ptr(total), stream_ptr(stream))
+    except _lib.YkError as err:
+        if err.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError("temperature_pick: indptr must start at >= 0 and never decrease, and every T must be "
+                         "finite and > 0") from None
+    return pick[:n], total[:n]
+
+
+def root_temper(p, nvalid, temps, stream=None):
+    """The root policy temperature on rows of compact priors (yk_root_temper), the device function k_root_noise
+    runs: device tensors p float32 [n, 3226] (row i compact over its first nvalid[i] entries), nvalid int32 [n],
+    temps float64 [n].  Returns float32 [n, 3226]: P' = f32(P ** (1 / T) / S) over those entries, 0 past them; a
+    row at T == 1.0 exactly is copied.  ValueError for a T that is not finite and > 0.  Synchronises."""
+    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != ACTION_SIZE:
+        raise TypeError(f"root_temper takes p float32 [n, {ACTION_SIZE}]")
+    n = int(p.shape[0])
+    if nvalid.dtype != torch.int32 or temps.dtype != torch.float64 or nvalid.shape != (n,) or temps.shape != (n,):
+        raise TypeError("root_temper takes nvalid int32 [n] and temps float64 [n]")
+    out = torch.empty_like(p)
+    if n == 0:
+        return out
+    try:
+        call("yk_root_temper", ptr(p), ptr(nvalid), ptr(temps), n, ptr(out), stream_ptr(stream))
+    except _lib.YkError as err:
+        if err.code != _lib.YK_ERR_RANGE:
+            raise
+        raise ValueError("root_temper: every T must be finite and > 0") from None
+    return out
+
+
 __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_mask", "unpack_mask", "ended",
            "canonical", "score_table", "score_dice", "featurize", "key_hash", "hash_prior", "dirichlet_noise",
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
            "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice",
-           "examples_full_rows", "policies_take", "policy_prune", "fpu_pick", "_lib"]
+           "examples_full_rows", "policies_take", "policy_prune", "fpu_pick", "temperature_schedule",
+           "temperature_pick", "root_temper", "_lib"]
 
 
 def greedy_action(states):

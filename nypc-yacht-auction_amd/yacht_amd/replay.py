@@ -200,6 +200,65 @@ def fpu_knobs_of(args) -> dict:
     return dict(fpu_reduction=r, fpu_root_reduction=rr)
 
 
+MOVE_TEMPERATURE_RANGE = (0.05, 100.0)  # visit counts are 16-bit: 65535 ** 20 ~ 2e96 is finite in float64
+ROOT_TEMPERATURE_RANGE = (0.25, 10.0)
+
+
+def check_temperature_knobs(moveTemperature=None, moveTemperatureEarly=None, rootPolicyTemperature=None,
+                            rootPolicyTemperatureEarly=None, temperatureHalflife=None) -> dict:
+    """The self-play temperatures, checked, as SelfPlayEngine's keyword arguments.  Each schedule is
+    T(m) = final + (early - final) * 2 ** (-m / halflife) over the real move m: moveTemperature (the final value,
+    in [0.05, 100]; unset: off) draws a temp-1 move from N ** (1 / T), rootPolicyTemperature (in [0.25, 10];
+    unset: off) searches the self-play root with P ** (1 / T) renormalised.  An Early defaults to its final
+    value; temperatureHalflife (> 0, shared) is required when an Early differs from its final value.
+    ValueError otherwise, and for an Early or a halflife without a final value (alone it would silently do
+    nothing)."""
+    def number(name, x, lo, hi):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number in [{lo}, {hi}] (unset: off), got {x!r}")
+        x = float(x)
+        if not lo <= x <= hi:  # (a NaN fails the comparison)
+            raise ValueError(f"{name} must lie in [{lo}, {hi}], got {x!r}")
+        return x
+
+    def pair(name, final, early, rng):
+        if final is None:
+            if early is not None:
+                raise ValueError(f"{name}Early needs {name}: without it the schedule is off and the early value "
+                                 "would silently do nothing")
+            return None, None
+        f = number(name, final, *rng)
+        return f, (f if early is None else number(name + "Early", early, *rng))
+
+    mf, me = pair("moveTemperature", moveTemperature, moveTemperatureEarly, MOVE_TEMPERATURE_RANGE)
+    rf, re_ = pair("rootPolicyTemperature", rootPolicyTemperature, rootPolicyTemperatureEarly, ROOT_TEMPERATURE_RANGE)
+    h = temperatureHalflife
+    if h is not None:
+        if mf is None and rf is None:
+            raise ValueError("temperatureHalflife needs moveTemperature or rootPolicyTemperature: without a "
+                             "schedule it would silently do nothing")
+        if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, float, np.integer, np.floating)):
+            raise ValueError(f"temperatureHalflife must be a number > 0, got {h!r}")
+        h = float(h)
+        if not 0.0 < h < float("inf"):  # (a NaN fails the comparison)
+            raise ValueError(f"temperatureHalflife must be finite and > 0, got {temperatureHalflife!r}")
+    elif (mf is not None and me != mf) or (rf is not None and re_ != rf):
+        raise ValueError("temperatureHalflife (> 0) is required when an Early temperature differs from its final "
+                         "value")
+    return dict(move_temperature=mf, move_temperature_early=me, root_policy_temperature=rf,
+                root_policy_temperature_early=re_, temperature_halflife=h)
+
+
+def temperature_knobs_of(args) -> dict:
+    """args.moveTemperature / moveTemperatureEarly / rootPolicyTemperature / rootPolicyTemperatureEarly /
+    temperatureHalflife, checked, as SelfPlayEngine's keyword arguments (self-play and the held-out games only:
+    the arenas, the plugin and the reanalysis pass nothing)."""
+    get = args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+    return check_temperature_knobs(get("moveTemperature", None), get("moveTemperatureEarly", None),
+                                   get("rootPolicyTemperature", None), get("rootPolicyTemperatureEarly", None),
+                                   get("temperatureHalflife", None))
+
+
 def check_ema_knobs(emaDecay=0.0, emaEvery=1):
     """(decay, every) of the averaged weights as (float, int): emaDecay in [0, 1) (0 / unset:
     off - the net that plays is the raw iterate), emaEvery an int >= 1 (the shadow moves after every emaEvery-th
