@@ -28,6 +28,7 @@
 #include "yk_forced.h"
 #include "yk_fpu.h"
 #include "yk_net.h"
+#include "yk_optarg.h"
 #include "yk_temper.h"
 
 #define YK_MAX_GROUPS 8
@@ -785,21 +786,13 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
     }
 }
 
-// FD: ForcedDev for the FORCED instantiation (the launches of a full self-play move with forced playouts) and
-// nothing for the default one, whose arguments - and with them its code - are what they were without the
-// feature (one more argument, even unread, changes the register allocation).
-__device__ __forceinline__ ForcedDev forced_arg() { return ForcedDev{0.0, 0.0}; }
-__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd) { return fd; }
-// and FpuDev, after it, for the FPU instantiations: the pack is (), (ForcedDev), (FpuDev) or both
-__device__ __forceinline__ ForcedDev forced_arg(const FpuDev&) { return ForcedDev{0.0, 0.0}; }
-__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd, const FpuDev&) { return fd; }
-__device__ __forceinline__ FpuDev fpu_arg() { return FpuDev{0.0, 0.0}; }
-__device__ __forceinline__ FpuDev fpu_arg(const ForcedDev&) { return FpuDev{0.0, 0.0}; }
-__device__ __forceinline__ const FpuDev& fpu_arg(const FpuDev& fp) { return fp; }
-__device__ __forceinline__ const FpuDev& fpu_arg(const ForcedDev&, const FpuDev& fp) { return fp; }
-template <bool FORCED, bool FPU, class... FD>
+// FD, the optional arguments (yk_optarg.h): ForcedDev for the FORCED instantiations (the launches of a full
+// self-play move with forced playouts), then FpuDev for the FPU ones; nothing for the default.
+using DescentArgs = yk::Args<ForcedDev, FpuDev>;
+template <class... FD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(sizeof...(FD) == (FORCED ? 1 : 0) + (FPU ? 1 : 0), "ForcedDev with FORCED, FpuDev with FPU, no further argument");
+    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, no further argument");
+    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>;
     const int lane = threadIdx.x & 63;
     // the wave's game as a scalar: every per-game base address is then scalar arithmetic, which keeps
     // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
@@ -811,17 +804,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
     const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
-    select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...), fpu_arg(fd...));
+    select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...));
 }
 
 // Leaf expansion (MCTS.py:84-115) and backup (MCTS.py:154-164) of this simulation, then -
 // when do_select - the next simulation's descent for the same game (one kernel boundary per
 // simulation fewer).  One wave per game.
 __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int lane, int t, int g);
-template <bool FORCED, bool FPU, class... FD>  // (FD: as k_select)
+template <class... FD>  // (FD: as k_select)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
     EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(sizeof...(FD) == (FORCED ? 1 : 0) + (FPU ? 1 : 0), "ForcedDev with FORCED, FpuDev with FPU, no further argument");
+    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, no further argument");
+    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>;
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
@@ -837,7 +831,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_W
             return;
         }
         wave_sync();  // this wave's backup writes (edges, slots, Ns) precede its descent's reads
-        select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, forced_arg(fd...), fpu_arg(fd...));
+        select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...));
     }
 }
 
@@ -1502,17 +1496,11 @@ __global__ __launch_bounds__(256) void k_root_sort(EngDev d) {
 // TEMPER (a move the move-selection temperature applies to, DESIGN.md s6h: a temp-1 move of self-play whose
 // T is not 1): the move is drawn from N^(1/T) over the same list, by the whole wave (wave_temper_pick,
 // yk_temper.h), with the one uniform the temp-1 draw takes; everything else, the record included, is as without.
-__device__ __forceinline__ const ForcedDev& forced_arg(const ForcedDev& fd, const TemperDev&) { return fd; }
-__device__ __forceinline__ ForcedDev forced_arg(const TemperDev&) { return ForcedDev{0.0, 0.0}; }
-__device__ __forceinline__ TemperDev temper_arg() { return TemperDev{nullptr, nullptr}; }
-__device__ __forceinline__ TemperDev temper_arg(const ForcedDev&) { return TemperDev{nullptr, nullptr}; }
-__device__ __forceinline__ const TemperDev& temper_arg(const TemperDev& td) { return td; }
-__device__ __forceinline__ const TemperDev& temper_arg(const ForcedDev&, const TemperDev& td) { return td; }
-template <bool PRUNE, bool TEMPER, class... FD>  // (FD: as k_select)
+template <class... FD>  // (as k_select's: ForcedDev for PRUNE, then TemperDev for TEMPER)
 __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, FD... fdp) {
-    static_assert(sizeof...(FD) == (PRUNE ? 1 : 0) + (TEMPER ? 1 : 0),
-                  "ForcedDev with PRUNE, TemperDev with TEMPER, no further argument");
-    const ForcedDev fd = forced_arg(fdp...);
+    static_assert(yk::args_in(yk::Args<ForcedDev, TemperDev>{}, yk::Args<FD...>{}), "ForcedDev, then TemperDev, no further argument");
+    constexpr bool PRUNE = yk::has_arg<ForcedDev, FD...>, TEMPER = yk::has_arg<TemperDev, FD...>;
+    const ForcedDev fd = yk::opt_arg(ForcedDev{0.0, 0.0}, fdp...);
     __shared__ uint32_t vis_all[GAMES_PER_BLOCK][ASIZE];
     __shared__ double stage_all[TEMPER ? GAMES_PER_BLOCK : 1][TEMPER ? 64 : 1];  // wave_temper_pick's pieces of 64 terms
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1630,7 +1618,7 @@ __global__ __launch_bounds__(256) void k_move_end(EngDev d, int move, int kind, 
         if (!idle && !d.arena && move + 1 < d.temp_threshold) {  // (wave-uniform) a temp-1 move, as below
             Stream ru{d.seed, d.env_id[e], d.ctr[e]};
             const double u = ru.uniform53();
-            tpick = wave_temper_pick([&](int i) { return vis[i] & 0xFFFF; }, nvis, 1.0 / temper_arg(fdp...).move_t[move],
+            tpick = wave_temper_pick([&](int i) { return vis[i] & 0xFFFF; }, nvis, 1.0 / yk::get_arg<TemperDev>(fdp...).move_t[move],
                                      u, stage_all[w], lane, &ttotal);
         }
     }
@@ -1946,29 +1934,19 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
     const dim3 bb(256);
     if (sims <= 0) return YK_OK;
     // first-play urgency: every search of an engine it is set on runs the FPU instantiations
-    const bool fpu = eng->fpu_on;
-    const FpuDev fp{eng->fpu_r, eng->fpu_r_root};
+    // the descents' options (yk_optarg.h): the values of those that are on are the kernels' packs
+    const auto o_forced = yk::opt(forced != nullptr, forced ? *forced : ForcedDev{0.0, 0.0});
+    const auto o_fpu = yk::opt(eng->fpu_on, FpuDev{eng->fpu_r, eng->fpu_r_root});
     const auto select = [&](const EngDev& dd, hipStream_t s) {
-        if (forced && fpu)
-            hipLaunchKernelGGL((k_select<true, true, ForcedDev, FpuDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced, fp);
-        else if (forced)
-            hipLaunchKernelGGL((k_select<true, false, ForcedDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, *forced);
-        else if (fpu)
-            hipLaunchKernelGGL((k_select<false, true, FpuDev>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, fp);
-        else
-            hipLaunchKernelGGL((k_select<false, false>), game_grid(dd), bb, 0, s, dd, env_ids, ctr);
+        yk::with_opts([&](const auto&... o) {
+            hipLaunchKernelGGL((k_select<std::decay_t<decltype(o)>...>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, o...);
+        }, o_forced, o_fpu);
     };
     const auto expand_backup = [&](const EngDev& dd, hipStream_t s, int do_select) {
-        if (forced && fpu)
-            hipLaunchKernelGGL((k_expand_backup<true, true, ForcedDev, FpuDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids,
-                               ctr, *forced, fp);
-        else if (forced)
-            hipLaunchKernelGGL((k_expand_backup<true, false, ForcedDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr,
-                               *forced);
-        else if (fpu)
-            hipLaunchKernelGGL((k_expand_backup<false, true, FpuDev>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr, fp);
-        else
-            hipLaunchKernelGGL((k_expand_backup<false, false>), game_grid(dd), bb, 0, s, dd, do_select, env_ids, ctr);
+        yk::with_opts([&](const auto&... o) {
+            hipLaunchKernelGGL((k_expand_backup<std::decay_t<decltype(o)>...>), game_grid(dd), bb, 0, s, dd, do_select, env_ids,
+                               ctr, o...);
+        }, o_forced, o_fpu);
     };
     const auto root_noise = [&](const EngDev& dd, hipStream_t s, int phase) {
         return root_t ? yk_launch_root_temper(&dd, sizeof(dd), &eng->nz, sizeof(eng->nz), root_t, with_noise ? 1 : 0,
@@ -2327,17 +2305,10 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
         for (int g = 0; g < G; g++) {
             prof_mark(eng, g, KC_MOVE_END, st[g]);
             const bool prune = forcing && !fast && eng->forced_prune;
-            if (prune && temper)
-                hipLaunchKernelGGL((k_move_end<true, true, ForcedDev, TemperDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
-                                   0, fd, eng->td);
-            else if (prune)
-                hipLaunchKernelGGL((k_move_end<true, false, ForcedDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move, 0, fd);
-            else if (temper)
-                hipLaunchKernelGGL((k_move_end<false, true, TemperDev>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
-                                   fast ? YK_REC_FAST : 0, eng->td);
-            else
-                hipLaunchKernelGGL((k_move_end<false, false>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
-                                   fast ? YK_REC_FAST : 0);
+            yk::with_opts([&](const auto&... o) {  // (prune implies !fast)
+                hipLaunchKernelGGL((k_move_end<std::decay_t<decltype(o)>...>), game_grid(dg[g]), bb, 0, st[g], dg[g], move,
+                                   fast ? YK_REC_FAST : 0, o...);
+            }, yk::opt(prune, fd), yk::opt(temper, eng->td));
             YK_LAUNCHED();
             if (root_values) {  // the games with nmoves == move + 1; root[e] is still this move's root
                 prof_mark(eng, g, KC_ROOT_VALUE, st[g]);

@@ -7,6 +7,7 @@
 
 #include "yk_engine_dev.h"
 #include "yk_noise.h"
+#include "yk_optarg.h"
 #include "yk_temper.h"
 
 namespace {
@@ -23,15 +24,15 @@ namespace {
 // A root with Ns = 0 has had no scan yet: its summary first_j is recomputed from P' with the scan's
 // own f32 operations (the expansion's, lowest index among equals).  k_root_sort runs after phase 1,
 // so the root's order is P''s.
-// TEMPER (the root policy temperature; its argument is the table of T by move): P is first
+// TEMPER (the root policy temperature; the table of T by move in the pack, yk_optarg.h): P is first
 // replaced by f32(P^(1/T) / S) over the same compact set (block_temper_weights, yk_temper.h: P read from
 // memory once, the weights staged in LDS), and the noise then mixes from that rounded value - one launch
 // does both.  NOISE = false is the tempering alone, without the sampler.  T == 1.0 exactly, or a prior
-// whose weights do not sum to > 0, leaves P as it is.  <false, true> is the kernel the noise alone runs.
-__device__ __forceinline__ const double* temper_table(const double* root_t) { return root_t; }
-template <bool TEMPER, bool NOISE, class... TD>
+// whose weights do not sum to > 0, leaves P as it is.  <true>, the empty pack, is the kernel the noise alone runs.
+template <bool NOISE, class... TD>
 __global__ __launch_bounds__(NOISE_THREADS) void k_root_noise(EngDev d, NoiseDev nz, int move, int phase, TD... root_t) {
-    static_assert(sizeof...(TD) == (TEMPER ? 1 : 0) && (TEMPER || NOISE), "the table of T with TEMPER, else no further argument");
+    constexpr bool TEMPER = yk::has_arg<const double*, TD...>;
+    static_assert(yk::args_in(yk::Args<const double*>{}, yk::Args<TD...>{}) && (TEMPER || NOISE), "the table of T or nothing");
     static_assert(TEMPER_THREADS == NOISE_THREADS, "one workgroup shape");
     __shared__ double eta[NOISE ? ASIZE : 1];
     __shared__ double wsum[4];
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void k_root_noise(EngDev d, NoiseDev
     bool tempered = false;  // (block-uniform)
     double S = 0.0;
     if constexpr (TEMPER) {
-        const double T = temper_table(root_t...)[move];
+        const double T = yk::get_arg<const double*>(root_t...)[move];
         if (T != 1.0) {
             S = block_temper_weights(P, V, 1.0 / T, tw, tsum, [&](int j, float p) {
                 if (rec) nz.prior_before[rslot + compact_to_action(vi, j)] = p;
@@ -137,7 +138,7 @@ int yk_launch_root_noise(const void* engdev, size_t engdev_bytes, const void* no
     memcpy(&d, engdev, sizeof(d));
     memcpy(&nz, noisedev, sizeof(nz));
     if (d.e_hi <= d.e_lo) return YK_OK;
-    hipLaunchKernelGGL((k_root_noise<false, true>), dim3((unsigned)(d.e_hi - d.e_lo)), dim3(NOISE_THREADS), 0, stream, d,
+    hipLaunchKernelGGL((k_root_noise<true>), dim3((unsigned)(d.e_hi - d.e_lo)), dim3(NOISE_THREADS), 0, stream, d,
                        nz, move, phase);
     YK_LAUNCHED();
     return YK_OK;
@@ -155,9 +156,9 @@ int yk_launch_root_temper(const void* engdev, size_t engdev_bytes, const void* n
     if (d.e_hi <= d.e_lo) return YK_OK;
     const dim3 grid((unsigned)(d.e_hi - d.e_lo)), block(NOISE_THREADS);
     if (with_noise)
-        hipLaunchKernelGGL((k_root_noise<true, true, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
+        hipLaunchKernelGGL((k_root_noise<true, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
     else
-        hipLaunchKernelGGL((k_root_noise<true, false, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
+        hipLaunchKernelGGL((k_root_noise<false, const double*>), grid, block, 0, stream, d, nz, move, phase, root_t);
     YK_LAUNCHED();
     return YK_OK;
 }

@@ -202,6 +202,7 @@ using LossTgt = std::conditional_t<SOFT, SoftRows, const int32_t*>;
 // where x is made - the softmax, the loss and dlogits are then those of the valid actions alone, and
 // dlogits is exactly 0 elsewhere (expf(-inf - lse) = 0).  The bits ride with the target argument
 // (k_legal_bits wrote them), so without MASK the kernel and its arguments are what they were.
+// (A variant in the middle of the argument list, not an optional trailing argument: those are yk_optarg.h's.)
 template <class Tgt>
 struct LegalTgt {
     Tgt t;

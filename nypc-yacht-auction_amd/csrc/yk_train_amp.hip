@@ -41,6 +41,7 @@
 #include "yk_api.h"
 #include "yk_common.h"
 #include "yk_legal.h"
+#include "yk_optarg.h"
 #include "yk_train_amp.h"
 
 using namespace yk;
@@ -636,7 +637,8 @@ __device__ __forceinline__ void soft_row_prep(const SoftCsr& c, const int32_t* _
 }
 
 // Soft: nothing (hard targets), or (SoftCsr, const int32_t* idx): part HQ then also prepares the
-// tile's rows' targets (soft_tile_prep).  Without the pack the kernel is the code it was before it.// the tile's 16 rows, two per wave
+// tile's rows' targets (soft_tile_prep).  Without the pack the kernel is the code it was before it (yk_optarg.h).
+// the tile's 16 rows, two per wave
 __device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int lane, const SoftCsr& c,
                                                const int32_t* __restrict__ idx) {
 #pragma unroll
@@ -657,24 +659,14 @@ __device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int la
 struct LegalBits {
     const uint32_t* __restrict__ w;  // [B][LEGAL_LD]
 };
-template <class... E>
-struct legal_first : std::false_type {};
-template <class... R>
-struct legal_first<LegalBits, R...> : std::true_type {};
-template <class... R>
-__device__ __forceinline__ const uint32_t* legal_words(const LegalBits& l, const R&...) { return l.w; }
-template <class... R>
-__device__ __forceinline__ void soft_tile_prep(int row0, int B, int wave, int lane, const LegalBits&, const R&... r) {
-    soft_tile_prep(row0, B, wave, lane, r...);
-}
 constexpr int LMW = 17;  // mask words per row in LDS: a part's <= 26 column tiles span <= 14 words; odd stride
 static_assert(((PT + HQ - 1) / HQ * 16 + 16 + 31) / 32 <= LMW, "a head part's mask words");
 
 template <int H, class... Soft>
 __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft) {
     constexpr int SA = H + 8, KS = H / 32;
-    constexpr bool MASK = legal_first<Soft...>::value;
-    constexpr int NSOFT = (int)sizeof...(Soft) - (MASK ? 1 : 0);
+    static_assert(yk::args_in(yk::Args<LegalBits, SoftCsr, const int32_t*>{}, yk::Args<Soft...>{}), "LegalBits, then (SoftCsr, idx)");
+    constexpr bool MASK = yk::has_arg<LegalBits, Soft...>, SOFT = yk::has_arg<SoftCsr, Soft...>;
     __shared__ __attribute__((aligned(16))) _Float16 A[TR * SA];
     __shared__ float2 red[TW][TR];
     __shared__ uint32_t LM[MASK ? TR * LMW : 1];  // MASK: the tile's rows' mask words from word lw0 on
@@ -692,7 +684,7 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft
     if constexpr (MASK) {
         lw0 = (16 * (part * PT / HQ)) >> 5;
         if (!vpart) {
-            const uint32_t* lw = legal_words(soft...);
+            const uint32_t* lw = yk::get_arg<LegalBits>(soft...).w;
             for (int i = tid; i < TR * LMW; i += TTHR) {
                 const int r = i / LMW, w = lw0 + i % LMW;
                 LM[i] = row0 + r < B && w < LEGAL_LD ? lw[(long)(row0 + r) * LEGAL_LD + w] : 0u;
@@ -714,7 +706,8 @@ __global__ __launch_bounds__(TTHR) void k_amp_head(AmpDev d, int B, Soft... soft
             const int row = row0 + 4 * q + j;
             if (row < B) d.zv1[(long)row * VH + col] = r16(acc[j] + bias);
         }
-        if constexpr (NSOFT > 0) soft_tile_prep(row0, B, wave, lane, soft...);
+        if constexpr (SOFT)
+            soft_tile_prep(row0, B, wave, lane, yk::get_arg<SoftCsr>(soft...), yk::get_arg<const int32_t*>(soft...));
         return;
     }
     const int t0 = part * PT / HQ, t1 = (part + 1) * PT / HQ;
@@ -2001,15 +1994,10 @@ int amp_backward(AmpTrain* a, const yk_state_t* states, const int32_t* targets, 
     case HH:                                                                                                        \
         hipLaunchKernelGGL(k_amp_fwd<HH>, dim3(TT), dim3(TTHR), 0, s, d, states, idx, B, dropout, seed, step, row_base); \
         YK_LAUNCHED();                                                                                              \
-        if (legal && soft)                                                                                          \
-            hipLaunchKernelGGL((k_amp_head<HH, LegalBits, SoftCsr, const int32_t*>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, \
-                               B, lb, sv, idx);                                                                     \
-        else if (legal)                                                                                             \
-            hipLaunchKernelGGL((k_amp_head<HH, LegalBits>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, lb);           \
-        else if (soft)                                                                                              \
-            hipLaunchKernelGGL((k_amp_head<HH, SoftCsr, const int32_t*>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, sv, idx); \
-        else                                                                                                        \
-            hipLaunchKernelGGL(k_amp_head<HH>, dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B);                           \
+        yk::with_opts([&](const auto&... o) {                                                                       \
+            hipLaunchKernelGGL((k_amp_head<HH, std::decay_t<decltype(o)>...>), dim3(T, HQ + 1), dim3(TTHR), 0, s, d, B, \
+                               o...);                                                                               \
+        }, yk::opt(legal != nullptr, lb), yk::opt(soft != nullptr, sv, idx));                                       \
         YK_LAUNCHED();                                                                                              \
         if (soft)                                                                                                   \
             hipLaunchKernelGGL((k_amp_headbwd<HH, true>), dim3(T, BQ + 1), dim3(TTHR), 0, s, d, sv, values, idx, B,  \
