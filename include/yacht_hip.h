@@ -431,6 +431,35 @@ int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_re
  * Synchronises `stream`. */
 int yk_fpu_pick(const int64_t* indptr, const float* p, const int32_t* counts, const double* q, const int32_t* ns,
                 int64_t n, double cpuct, double reduction, int32_t* pick, int32_t* unvisited, void* stream);
+/* The score-margin utility (KataGo's score utility), a departure from the reference, opt-in; DESIGN.md section
+ * 6i.  Off (on = 0, the state of a new engine): nothing changes.  On, in EVERY search of this engine - yk_selfplay
+ * (full and fast moves), yk_arena (both trees of a dual-tree engine) and yk_mcts_search - at the one place a
+ * terminal value enters the search.  For a terminal state s, that is game_ended(s, 1) != 0, seen from `player`
+ * (+1 / -1), with w = weight in [0, 1] and c = scale, finite and > 0, in game points (a pip is 1000 points):
+ *   z = game_ended(s, player)                              (+-1; 1e-4 for a draw, for either player)
+ *   m = total_with_bonus(s, 0) - total_with_bonus(s, 1)    (int)
+ *   x = (double)(player * m) / c
+ *   g = x / (1.0 + fabs(x))
+ *   u = (1.0 - w) * z + w * g
+ * Every operation is one IEEE double operation, rounded on its own (no FMA; 1.0 - w is computed once on the
+ * host, the division is by c and not a multiplication by 1 / c), so numpy float64 gives the same bits; the squash
+ * is rational because division and addition are correctly rounded, which a device tanh does not promise.
+ * |u| <= 1.  A state is terminal when game_ended != 0, never when u != 0: at w = 1 a draw has u = 0 and is still
+ * terminal.  A descent that reaches a terminal state returns -u(s, 1) on the canonical board, still typed as a
+ * Python float; nothing else in the descent, the backup, the root scan, the node summaries, first-play urgency,
+ * forced playouts or the root value changes.  The records (values, the final result and totals) and the arena
+ * results stay the game's own.  weight = 0 is legal, is not off, and searches bit for bit as off does.  Lives in
+ * the engine, not in yk_engine_config_t.  NULL engine, a weight outside [0, 1], a scale <= 0, NaN or infinite
+ * values: YK_ERR_ARG, the engine unchanged.  Touches no device memory. */
+int yk_engine_set_score_utility(yk_engine_t* eng, int on, double weight, double scale);
+/* The rule alone, on n states given by the caller - the sibling of yk_ended: DEVICE states[n], players[n]
+ * (+1 / -1) -> DEVICE u[n], the utility of state i seen from players[i] and 0.0 where the state is not terminal,
+ * and margin[n] (may be NULL) = m, written for every state.  The same device function as the search kernels and
+ * the value targets; one thread per state; no atomics; equal inputs give equal bits.  The setter's checks on
+ * weight and scale, n < 0, or (n > 0) a NULL states, players or u: YK_ERR_ARG before anything touches the
+ * device.  Asynchronous on `stream`. */
+int yk_score_utility(const yk_state_t* states, const int32_t* players, int n, double weight, double scale, double* u,
+                     int32_t* margin, void* stream);
 /* The two self-play temperatures (AlphaZero / KataGo), a departure from the reference, opt-in; DESIGN.md
  * section 6h.  Off (the state of a new engine): nothing changes.  Both follow one schedule shape over the
  * 0-based index m of the real move, in host float64:
@@ -510,7 +539,9 @@ int yk_engine_stats(yk_engine_t* eng, int64_t* out);
  * 5 root picks of the last batch that took a forced edge, 6 visits its pruning took off the recorded counts
  *   (yk_engine_set_forced_playouts; both 0 with it off, and after yk_arena)
  * 7 descent picks of the last batch (every depth) that first-play urgency gave to the unvisited candidate,
- *   8 picks its rule decided: nodes with both kinds of edge (yk_engine_set_fpu; both 0 with it off) */
+ *   8 picks its rule decided: nodes with both kinds of edge (yk_engine_set_fpu; both 0 with it off)
+ * 9 descents of the last batch that ended at a terminal state and returned a score-margin utility
+ *   (yk_engine_set_score_utility; 0 with it off - the default instantiations do not count) */
 int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n);
 /* Copies the last episode batch to HOST arrays (any may be NULL):
  *   states[n][max_moves][8]  canonical board of each example (Coach.py:57,61)
@@ -610,6 +641,19 @@ int yk_examples_policies(const void* images, int n_images, int n_envs, int max_m
 int yk_examples_value_targets(const void* images, int n_images, int n_envs, int max_moves, int sims,
                               int64_t n_games, int64_t skip, int64_t n_examples, double beta, double lambda,
                               float* values, float* root_values, int64_t* n_missing, void* stream);
+/* yk_examples_value_targets under the score-margin utility (the rule at
+ * yk_engine_set_score_utility): the same kernel, reading U_t wherever the formulas above read Z_t = p_t * z_t,
+ *     g1  = the rule's g for player 1 from the game's final board in the images (one value per game)
+ *     U_t = (1.0 - weight) * Z_t + weight * g1
+ * so at (beta, lambda) = (0, 1) values[k] = (float)(p_t * U_t), no root value is read and none can be missing; at
+ * other (beta, lambda) the recursion and the mix run on U.  The recorded root values are already in utility units
+ * when the engine that played searched under the same knobs.  root_values and n_missing behave as above.  The
+ * setter's checks on weight and scale, and every check of yk_examples_value_targets: YK_ERR_ARG before anything
+ * touches the device.  weight = 0 gives yk_examples_value_targets' bits.  Synchronises `stream`. */
+int yk_examples_utility_targets(const void* images, int n_images, int n_envs, int max_moves, int sims,
+                                int64_t n_games, int64_t skip, int64_t n_examples, double beta, double lambda,
+                                double weight, double scale, float* values, float* root_values, int64_t* n_missing,
+                                void* stream);
 /* The examples of full moves (playout cap).  Images, n_games and the example numbering
  * are yk_examples_from_records' with skip = 0.  DEVICE idx[0 .. n_full-1] = the numbers, ascending, of the
  * examples whose info[..][6] lacks YK_REC_FAST (at most `capacity` are written; idx == NULL: count only), HOST

@@ -27,6 +27,7 @@
 #include "yk_engine_dev.h"
 #include "yk_forced.h"
 #include "yk_fpu.h"
+#include "yk_utility.h"
 #include "yk_net.h"
 #include "yk_optarg.h"
 #include "yk_temper.h"
@@ -522,9 +523,13 @@ __device__ __forceinline__ void select_none(const EngDev& d, int e, int lane) {
 // visited and an unvisited edge, on every path: root_scan, and the full scan, which then keeps two running bests
 // (the visited u, the unvisited x) and the two integer sums per lane.  A node at Ns = 0 (the summary's, or a
 // full scan over unvisited edges only) and a node whose edges are all visited come out as before.
-template <bool FORCED, bool FPU>
+//
+// UTIL: the score-margin utility (the arithmetic of yk_utility.h) at the one place a terminal value
+// enters the search, the Es test below: the descent returns -u(s, 1) in place of -Es, still a Python float, and
+// counts the return.  Whether the state is terminal stays Es != 0.  Nothing else of the descent reads it.
+template <bool FORCED, bool FPU, bool UTIL>
 __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, int t, int g, const uint32_t* env_ids,
-                                            uint64_t* ctr_arr, const ForcedDev& fd, const FpuDev& fp) {
+                                            uint64_t* ctr_arr, const ForcedDev& fd, const FpuDev& fp, const UtilDev& ud) {
     // FORCED: 1 when the root's pick was a forced edge.  (Declared first: among the locals below it reorders two
     // phi nodes of the default instantiation, and the register allocation with them.)
     int fpick = 0;
@@ -590,7 +595,12 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
         if (!have) {
             const double es = game_ended(s, 1);  // Es (MCTS.py:78-82)
             if (es != 0.0) {
-                res = PyV{-es, T_F64};
+                if constexpr (UTIL) {  // (s is canonical: seen from player 1)
+                    res = PyV{-score_utility(s, 1, es, ud), T_F64};
+                    if (lane == 0) atomicAdd(ud.terminals + e, 1ull);
+                } else {
+                    res = PyV{-es, T_F64};
+                }
                 break;
             }
             const uint64_t hsh = index_hash(s);
@@ -787,12 +797,13 @@ __device__ __forceinline__ void select_game(const EngDev& d, int e, int lane, in
 }
 
 // FD, the optional arguments (yk_optarg.h): ForcedDev for the FORCED instantiations (the launches of a full
-// self-play move with forced playouts), then FpuDev for the FPU ones; nothing for the default.
-using DescentArgs = yk::Args<ForcedDev, FpuDev>;
+// self-play move with forced playouts), then FpuDev for the FPU ones, then UtilDev for the
+// score-margin utility's; nothing for the default.
+using DescentArgs = yk::Args<ForcedDev, FpuDev, UtilDev>;
 template <class... FD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_select(EngDev d, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, no further argument");
-    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>;
+    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, then UtilDev, no further argument");
+    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>, UTIL = yk::has_arg<UtilDev, FD...>;
     const int lane = threadIdx.x & 63;
     // the wave's game as a scalar: every per-game base address is then scalar arithmetic, which keeps
     // the descent's vector registers for its scan (no scratch; as a vector value: 20 bytes per lane)
@@ -804,7 +815,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     const int t = __builtin_amdgcn_readfirstlane(tree_of(d, e));
     const int g = __builtin_amdgcn_readfirstlane((int)d.gen[t]);
-    select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...));
+    select_game<FORCED, FPU, UTIL>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...),
+                                       yk::opt_arg(UtilDev{1.0, 0.0, 1.0, nullptr}, fd...));
 }
 
 // Leaf expansion (MCTS.py:84-115) and backup (MCTS.py:154-164) of this simulation, then -
@@ -814,8 +826,8 @@ __device__ __forceinline__ void expand_backup_game(const EngDev& d, int e, int l
 template <class... FD>  // (FD: as k_select)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_WPE))) void k_expand_backup(
     EngDev d, int do_select, const uint32_t* env_ids, uint64_t* ctr_arr, FD... fd) {
-    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, no further argument");
-    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>;
+    static_assert(yk::args_in(DescentArgs{}, yk::Args<FD...>{}), "ForcedDev, then FpuDev, then UtilDev, no further argument");
+    constexpr bool FORCED = yk::has_arg<ForcedDev, FD...>, FPU = yk::has_arg<FpuDev, FD...>, UTIL = yk::has_arg<UtilDev, FD...>;
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane(d.e_lo + blockIdx.x * GAMES_PER_BLOCK + (threadIdx.x >> 6));  // (as k_select)
     if (e >= d.e_hi) return;
@@ -831,7 +843,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(YK_EXPAND_W
             return;
         }
         wave_sync();  // this wave's backup writes (edges, slots, Ns) precede its descent's reads
-        select_game<FORCED, FPU>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...));
+        select_game<FORCED, FPU, UTIL>(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg(ForcedDev{0.0, 0.0}, fd...), yk::opt_arg(FpuDev{0.0, 0.0}, fd...),
+                                       yk::opt_arg(UtilDev{1.0, 0.0, 1.0, nullptr}, fd...));
     }
 }
 
@@ -1823,6 +1836,9 @@ struct yk_engine {
     int64_t fast_moves = 0;      // lock-step moves of the last batch that ran with the fast cap
     double forced_k = 0.0;       // forced playouts (yk_engine_set_forced_playouts; 0: off) at the self-play roots
     bool forced_prune = true;    // of full moves, and whether k_move_end prunes the move's counts
+    bool util_on = false;        // the score-margin utility (yk_engine_set_score_utility) at the
+    double util_w = 0.0, util_c = 1.0;  // terminal states of every search of this engine: the weight and the scale
+    unsigned long long* util_terminals = nullptr;  // [E] terminal descents that returned a utility (counter 9)
     bool fpu_on = false;         // first-play urgency (yk_engine_set_fpu) in every search of this
     double fpu_r = 0.0, fpu_r_root = 0.0;  // engine: the reduction at interior nodes and at depth 0
     // the self-play temperatures (yk_engine_set_temperatures): each schedule's T by move, M
@@ -1924,7 +1940,8 @@ int check_errors(yk_engine* eng, hipStream_t s) {
 // fused descent whatever the root-scan mode.  -1: no noise launch is made.
 // forced (a full self-play move with forced playouts): the descents are the FORCED
 // instantiations; every other caller runs the unforced ones, whose code the feature leaves as it was.
-// Whether they are the FPU ones is the engine's state (yk_engine_set_fpu), the same for every caller.
+// Whether they are the FPU ones is the engine's state (yk_engine_set_fpu), the same for every caller; so is
+// whether they are the score-margin utility's (yk_engine_set_score_utility).
 // root_t (a self-play move under the root policy temperature, DESIGN.md s6h: the device table of T by move):
 // the two launches of noise_move are the tempered forms of k_root_noise - with `with_noise` the one that also
 // mixes the noise, else the one without the sampler.  NULL: the launches are the noise's own, as before.
@@ -1937,16 +1954,17 @@ int run_sims(yk_engine* eng, int G, const hipStream_t* st, int sims, const uint3
     // the descents' options (yk_optarg.h): the values of those that are on are the kernels' packs
     const auto o_forced = yk::opt(forced != nullptr, forced ? *forced : ForcedDev{0.0, 0.0});
     const auto o_fpu = yk::opt(eng->fpu_on, FpuDev{eng->fpu_r, eng->fpu_r_root});
+    const auto o_util = yk::opt(eng->util_on, UtilDev{1.0 - eng->util_w, eng->util_w, eng->util_c, eng->util_terminals});
     const auto select = [&](const EngDev& dd, hipStream_t s) {
         yk::with_opts([&](const auto&... o) {
             hipLaunchKernelGGL((k_select<std::decay_t<decltype(o)>...>), game_grid(dd), bb, 0, s, dd, env_ids, ctr, o...);
-        }, o_forced, o_fpu);
+        }, o_forced, o_fpu, o_util);
     };
     const auto expand_backup = [&](const EngDev& dd, hipStream_t s, int do_select) {
         yk::with_opts([&](const auto&... o) {
             hipLaunchKernelGGL((k_expand_backup<std::decay_t<decltype(o)>...>), game_grid(dd), bb, 0, s, dd, do_select, env_ids,
                                ctr, o...);
-        }, o_forced, o_fpu);
+        }, o_forced, o_fpu, o_util);
     };
     const auto root_noise = [&](const EngDev& dd, hipStream_t s, int phase) {
         return root_t ? yk_launch_root_temper(&dd, sizeof(dd), &eng->nz, sizeof(eng->nz), root_t, with_noise ? 1 : 0,
@@ -2151,6 +2169,8 @@ constexpr int YK_FPARTS_MAX = 4;
     A(d.seat, E);
     A(d.idle, E);
     A(d.gstats, E * GST);
+    A(eng->util_terminals, E);
+    YK_HIP(hipMemset(eng->util_terminals, 0, sizeof(unsigned long long) * E));
     A(d.err, 1);
     A(eng->done_count, 1);
     A(eng->mcts_env, E);
@@ -2279,6 +2299,7 @@ int play_batch(yk_engine* eng, uint64_t seed, uint32_t env_base, hipStream_t s) 
         YK_HIP(hipMemsetAsync(eng->nz.prior_before, 0, nb, s));
         YK_HIP(hipMemsetAsync(eng->nz.prior_after, 0, nb, s));
     }
+    YK_HIP(hipMemsetAsync(eng->util_terminals, 0, sizeof(unsigned long long) * (size_t)d.E, s));  // (with the gstats)
     hipLaunchKernelGGL(k_reset, dim3((d.E + 255) / 256), dim3(256), 0, s, d, 1, env_base);
     YK_LAUNCHED();
     if (G > 1) {  // the group streams start after the reset on the caller's stream
@@ -2369,6 +2390,14 @@ int yk_engine_set_fpu(yk_engine_t* eng, int on, double reduction, double root_re
     eng->fpu_on = on != 0;
     eng->fpu_r = reduction;
     eng->fpu_r_root = root_reduction;
+    return YK_OK;
+}
+
+int yk_engine_set_score_utility(yk_engine_t* eng, int on, double weight, double scale) {
+    if (!eng || !score_knobs_ok(weight, scale)) return YK_ERR_ARG;  // (a NaN fails the comparisons)
+    eng->util_on = on != 0;
+    eng->util_w = weight;
+    eng->util_c = scale;
     return YK_OK;
 }
 
@@ -2552,14 +2581,18 @@ int yk_engine_counters(yk_engine_t* eng, int64_t* out, int n) {
     YK_HIP(hipMemcpy(gs.data(), d.gstats, sizeof(uint64_t) * gs.size(), hipMemcpyDeviceToHost));
     // scan edges; expansions by prior path: window, sparse, general; the playout cap's fast moves; root picks
     // that took a forced edge and visits the pruning took off the recorded counts; descent picks
-    // first-play urgency gave to the unvisited candidate, and picks its rule decided
-    int64_t c[9] = {0, 0, 0, 0, eng->fast_moves, 0, 0, 0, 0};
+    // first-play urgency gave to the unvisited candidate, and picks its rule decided; descents
+    // that ended at a terminal state and returned a score-margin utility
+    std::vector<unsigned long long> ut((size_t)d.E);
+    YK_HIP(hipMemcpy(ut.data(), eng->util_terminals, sizeof(unsigned long long) * ut.size(), hipMemcpyDeviceToHost));
+    int64_t c[10] = {0, 0, 0, 0, eng->fast_moves, 0, 0, 0, 0, 0};
     for (int e = 0; e < d.E; e++) {
         c[0] += (int64_t)gs[(size_t)e * GST + 8];
         for (int k = 0; k < 3; k++) c[1 + k] += (int64_t)gs[(size_t)e * GST + 9 + k];
         for (int k = 0; k < 4; k++) c[5 + k] += (int64_t)gs[(size_t)e * GST + 12 + k];
+        c[9] += (int64_t)ut[e];
     }
-    for (int i = 0; i < n; i++) out[i] = i < 9 ? c[i] : 0;
+    for (int i = 0; i < n; i++) out[i] = i < 10 ? c[i] : 0;
     return YK_OK;
 }
 
@@ -2688,6 +2721,7 @@ int yk_mcts_reset(yk_engine_t* eng) {
     YK_HIP(hipMemset(d.err, 0, sizeof(uint32_t)));
     YK_HIP(hipMemset(d.hidx[0], 0, sizeof(uint32_t) * (size_t)d.T * d.HCAP));
     YK_HIP(hipMemset(d.done, 0, (size_t)d.E));
+    YK_HIP(hipMemset(eng->util_terminals, 0, sizeof(unsigned long long) * (size_t)d.E));  // (with the gstats)
     hipLaunchKernelGGL(k_reset, dim3((d.E + 255) / 256), dim3(256), 0, 0, d, 0, 0u);
     YK_LAUNCHED();
     YK_HIP(hipDeviceSynchronize());

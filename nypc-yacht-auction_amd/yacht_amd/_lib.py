@@ -153,14 +153,18 @@ SIGNATURES = {
     "yk_examples_check_legal": [P, P, P, P, P, P, C.c_int64, P, P, P],
     "yk_examples_metrics_legal": [P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int64, P, P, P],
     "yk_net_evaluate_legal": [P, P, P, P, P, P, P, P, C.c_int64, I, P, P, P],
+    "yk_engine_set_score_utility": [P, I, C.c_double, C.c_double],
+    "yk_score_utility": [P, P, I, C.c_double, C.c_double, P, P, P],
+    "yk_examples_utility_targets": [P, I, I, I, I, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, P, P, P, P],
 }
 _RESTYPE = {"yk_version": C.c_char_p, "yk_rng_draw64": C.c_uint64, "yk_engine_record_bytes": C.c_int64,
             "yk_trainer_step_count": C.c_int64}
 
 # added in rounds 5-6, with the soft policy targets, the root noise, the symmetry augmentation, the
 # search-value targets, the held-out evaluation, the weighted sampling, the reanalysis, the playout cap, the
-# averaged weights, the forced playouts, the first-play urgency, the legal-move mask and the self-play
-# temperatures (A/B baselines may predate them)
+# averaged weights, the forced playouts, the first-play urgency, the legal-move mask, the self-play
+# temperatures and the score-margin utility (A/B baselines may predate them)
 _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk_trainer_step_soft",
           "yk_engine_root_priors", "yk_dirichlet_noise", "yk_examples_augment", "yk_examples_value_targets",
           "yk_net_logits", "yk_examples_metrics", "yk_net_evaluate", "yk_sample_weights", "yk_sample_cdf",
@@ -171,7 +175,7 @@ _NEWER = {"yk_engine_counters", "yk_net_errors", "yk_trainer_backward_soft", "yk
           "yk_policy_prune", "yk_engine_set_fpu", "yk_fpu_pick", "yk_trainer_set_legal_mask",
           "yk_examples_check_legal", "yk_examples_metrics_legal", "yk_net_evaluate_legal",
           "yk_engine_set_temperatures", "yk_engine_temperatures", "yk_temperature_schedule", "yk_temperature_pick",
-          "yk_root_temper"}
+          "yk_root_temper", "yk_engine_set_score_utility", "yk_score_utility", "yk_examples_utility_targets"}
 _lib = None
 
 

@@ -122,9 +122,10 @@ class MCTSArena:
         prior = "hash" if not uses_net or getattr(self.nnet, "yk_prior", None) == "hash" else "net"
         net = None if prior == "hash" else self.nnet.yk_net()
         sims = self.args.numMCTSSims if "mcts" in (self.agent, self.opponent) else 1
-        from .replay import fpu_knobs_of
+        from .replay import fpu_knobs_of, score_knobs_of
+        # (first-play urgency, DESIGN.md 6g: args.fpuReduction; the score-margin utility, 6i: args.scoreUtility)
         return SelfPlayEngine(n, sims, self.args.get("cpuct", 1.0), 0, net=net, prior=prior, max_moves=64,
-                              **fpu_knobs_of(self.args))  # (first-play urgency, DESIGN.md 6g: args.fpuReduction)
+                              **fpu_knobs_of(self.args), **score_knobs_of(self.args))
 
     def play_batch(self, agent_seats) -> dict:
         """One device batch; agent_seats[i] in {1, -1}.  Returns the engine's arena results."""
@@ -178,11 +179,13 @@ class GatingArena:
             seats = np.where(np.arange(lo, hi) < half, 1, -1).astype(np.int32)
             hashed = getattr(self.pnet, "yk_prior", None) == "hash" and getattr(self.nnet, "yk_prior", None) == "hash"
             a = self.args
-            from .replay import fpu_knobs_of
+            from .replay import fpu_knobs_of, score_knobs_of
             eng = SelfPlayEngine(hi - lo, a.numMCTSSims, a.get("cpuct", 1.0), 0,
                                  net=None if hashed else self.pnet.yk_net(), prior="hash" if hashed else "net",
                                  opponent_net=None if hashed else self.nnet.yk_net(), max_moves=48, dual_trees=True,
-                                 **fpu_knobs_of(a))  # (both seats search under args.fpuReduction)
+                                 # (both seats search under args.fpuReduction, DESIGN.md 6g, and args.scoreUtility, 6i;
+                                 # the tallies count the games' own results)
+                                 **fpu_knobs_of(a), **score_knobs_of(a))
             try:
                 eng.arena(seats, self.game.rng.seed, base + lo, agent="mcts", opponent="mcts")
                 self.last = eng.arena_results()

@@ -25,6 +25,10 @@ any number of ranks (one process per GPU, torch.distributed):
 * first-play urgency (opt-in, ``args.fpuReduction``, ``fpuRootReduction``; not in the reference):
   an unvisited edge starts from the visited children's visit-weighted mean less a reduction, not from 0 - in
   everything that searches: self-play, the held-out games, the reanalysis, the gate, ``MCTSArena``, the plugin.
+* score-margin utility (opt-in, ``args.scoreUtility``, ``scoreScale``; not in the reference): a
+  bounded function of the final point margin is blended into the outcome, at the terminal states of every search
+  (self-play, the held-out games, the reanalysis, the gate, ``MCTSArena``, the plugin) and in the value targets;
+  the records, the examples files, the gate's tallies and ``NNetWrapper.evaluate`` keep the outcome.
 * self-play temperatures (opt-in, ``args.moveTemperature`` / ``moveTemperatureEarly``,
   ``rootPolicyTemperature`` / ``rootPolicyTemperatureEarly``, ``temperatureHalflife``; not in the reference;
   DESIGN.md 6h): a temp-1 move is drawn from N^(1/T) and the self-play root searched with P^(1/T) renormalised,
@@ -115,6 +119,11 @@ class Coach:
         from .replay import check_fpu_knobs
         self.fpu_reduction, self.fpu_root_reduction = check_fpu_knobs(args.get("fpuReduction", None),
                                                                       args.get("fpuRootReduction", None))
+        # the score-margin utility in every search made for this Coach and in its value targets.
+        # Unset: off
+        from .replay import check_score_knobs
+        self.score_utility, self.score_scale = check_score_knobs(args.get("scoreUtility", None),
+                                                                 args.get("scoreScale", None))
         # the self-play temperatures: self-play and the held-out games only.  Unset: off
         from .replay import temperature_knobs_of
         self.temperature_knobs = temperature_knobs_of(args)
@@ -127,7 +136,8 @@ class Coach:
         from .replay import check_mask_knobs
         self.mask_illegal = check_mask_knobs(args.get("maskIllegal", False))
         # {"searched", "kept", "sims"} of the last selfPlayExamples (this rank's sims); with forcedPlayoutsK also
-        # {"forced_picks", "pruned_visits"} and with fpuReduction {"fpu_unvisited_picks", "fpu_picks"} (this rank's)
+        # {"forced_picks", "pruned_visits"}, with fpuReduction {"fpu_unvisited_picks", "fpu_picks"} and with
+        # scoreUtility {"utility_terminals"} (this rank's)
         self.last_selfplay = None
         self.last_reanalysis = None  # [{"item", "n", "reanalysed", "n_empty"}] of the last iteration
         # held-out evaluation: holdoutEps more self-play games per iteration, kept out of training
@@ -169,6 +179,8 @@ class Coach:
                               forced_playouts_k=self.forced_k, forced_prune=self.forced_prune,
                               # first-play urgency; the same for the held-out games
                               fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction,
+                              # the score-margin utility; the same for the held-out games
+                              score_utility=self.score_utility, score_scale=self.score_scale,
                               # the move-selection and root policy temperatures; the same for the held-out games
                               **self.temperature_knobs)
 
@@ -206,7 +218,8 @@ class Coach:
         gathered = D.allgather_records(img)
         shard = examples_from_images(gathered, c, GAME_MOVES, self.args.numMCTSSims, n_games=n, maxlen=maxlen,
                                      value_mix=self.value_mix, value_lambda=self.value_lambda,
-                                     full_only=self.playout_fast_sims > 0)
+                                     full_only=self.playout_fast_sims > 0, score_utility=self.score_utility,
+                                     score_scale=self.score_scale)
         self.last_selfplay = dict(searched=shard.n_searched, kept=len(shard), sims=sims_run)
         forced = ""
         if self.forced_k > 0:
@@ -215,6 +228,9 @@ class Coach:
         if self.fpu_reduction is not None:
             self.last_selfplay.update(fpu_unvisited_picks=st["fpu_unvisited_picks"], fpu_picks=st["fpu_picks"])
             forced += ", %d of %d first-play-urgency picks unvisited" % (st["fpu_unvisited_picks"], st["fpu_picks"])
+        if self.score_utility is not None:
+            self.last_selfplay.update(utility_terminals=st["utility_terminals"])
+            forced += ", %d terminal descents returned a score utility" % st["utility_terminals"]
         log.info("SELF-PLAY %d moves searched, %d examples kept, %d lock-step sims run (this rank)%s"
                  % (shard.n_searched, len(shard), sims_run, forced))
         return shard
@@ -244,7 +260,8 @@ class Coach:
                 if m:
                     H[j] = reanalyse(item, idx, net=net, prior=prior, sims=self.reanalyse_sims,
                                      cpuct=self.args.cpuct, seed=self.game.rng.seed, env_base=self._streams(m),
-                                     fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction)
+                                     fpu_reduction=self.fpu_reduction, fpu_root_reduction=self.fpu_root_reduction,
+                                     score_utility=self.score_utility, score_scale=self.score_scale)
                     report.append(dict(item=j, n=n, reanalysed=m, n_empty=H[j].reanalysis["n_empty"]))
             base += n
         self.last_reanalysis = report
@@ -382,6 +399,9 @@ class Coach:
             log.warning(f'File "{examplesFile}" with trainExamples not found!')
             return
         log.info("Loading done!")
+        if self.score_utility is not None:  # (as below: the files hold the outcome only)
+            log.warning("scoreUtility is set, but the examples file holds outcomes only: the "
+                        f"{len(self.trainExamplesHistory)} reloaded iteration(s) train on outcomes")
         if self._value_targets_on():  # (a resumed run must still start: the files hold the outcome only)
             log.warning("valueMix / valueLambda are set, but the examples file holds outcomes only: the "
                         f"{len(self.trainExamplesHistory)} reloaded iteration(s) train on outcomes")

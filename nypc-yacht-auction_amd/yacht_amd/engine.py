@@ -26,7 +26,8 @@ class SelfPlayEngine:
                  dirichlet_eps: float = 0.0, record_root_values: bool = False, playout_fast_sims: int = 0,
                  playout_full_prob: float = 1.0, forced_playouts_k: float = 0.0, forced_prune: bool = True,
                  fpu_reduction=None, fpu_root_reduction=None, move_temperature=None, move_temperature_early=None,
-                 root_policy_temperature=None, root_policy_temperature_early=None, temperature_halflife=None):
+                 root_policy_temperature=None, root_policy_temperature_early=None, temperature_halflife=None,
+                 score_utility=None, score_scale=None):
         if prior not in ("net", "hash"):
             raise ValueError("prior is 'net' (YachtNNet on MFMA) or 'hash' (deterministic test prior)")
         if prior == "net" and net is None:
@@ -102,6 +103,25 @@ class SelfPlayEngine:
         except Exception:
             self.close()
             raise
+        # the score-margin utility at the terminal states of every search of this engine - run() (full and fast
+        # moves), arena() (both trees) and yk_mcts_search: a terminal descent returns
+        # (1 - score_utility) * z + score_utility * x / (1 + |x|), x = the final margin / score_scale, in place of
+        # the outcome z.  The records and the arena results stay the game's own.  None is off; a weight of 0 is legal,
+        # is not off and searches as off does
+        if score_utility is None and score_scale is not None:
+            self.close()
+            raise ValueError("score_scale needs score_utility: alone it would silently do nothing")
+        if score_utility is not None and score_scale is None:
+            self.close()
+            raise ValueError("score_utility needs score_scale (game points, > 0): there is no default scale")
+        self.score_utility = None if score_utility is None else float(score_utility)
+        self.score_scale = None if score_scale is None else float(score_scale)
+        if self.score_utility is not None:
+            try:
+                call("yk_engine_set_score_utility", self.handle, 1, self.score_utility, self.score_scale)
+            except Exception:
+                self.close()
+                raise
         self.opponent_net = opponent_net
         if opponent_net is not None:
             # MCTS vs MCTS with two nets, each seat its own tree (the gating arena, Coach.py:117-139)
@@ -178,8 +198,10 @@ class SelfPlayEngine:
     # pruning took off its recorded counts
     # fpu_unvisited_picks / fpu_picks: the last batch's descent picks (every depth) that first-play urgency gave
     # to the unvisited candidate, and the picks its rule decided - nodes with both kinds of edge
+    # utility_terminals: the last batch's descents that ended at a terminal state and returned a score-margin
+    # utility (0 with it off)
     COUNTER_NAMES = ("scan_edges", "prior_window", "prior_sparse", "prior_general", "fast_moves", "forced_picks",
-                     "pruned_visits", "fpu_unvisited_picks", "fpu_picks")
+                     "pruned_visits", "fpu_unvisited_picks", "fpu_picks", "utility_terminals")
 
     def stats(self) -> dict:
         out = np.zeros(16, dtype=np.int64)

@@ -92,6 +92,24 @@ def ended(states, players):
     return r, tot
 
 
+def score_utility(states, players, weight: float, scale: float):
+    """The score-margin utility of each state seen from its player (yk_score_utility): states int64[n, 8]
+    (or uint64 words), players +1 / -1 (a scalar is broadcast), weight w in [0, 1], scale c > 0 in game points ->
+    (u float64[n], margin int32[n]).  u = (1 - w) * game_ended + w * x / (1 + |x|), x = player * margin / c; 0.0 for a
+    state that is not terminal (its margin is still written).  ValueError for a bad weight or scale."""
+    from .replay import check_score_knobs
+    if weight is None or scale is None:
+        raise ValueError("score_utility needs a weight and a scale")
+    w, c = check_score_knobs(weight, scale)
+    st = _dev(states, torch.int64).reshape(-1, 8)
+    n = st.shape[0]
+    pl = _bcast(players, n, torch.int32)
+    u = torch.zeros(n, dtype=torch.float64, device="cuda")
+    m = torch.zeros(n, dtype=torch.int32, device="cuda")
+    call("yk_score_utility", ptr(st), ptr(pl), n, w, c, ptr(u), ptr(m), stream_ptr())
+    return u, m
+
+
 def canonical(states, players):
     st = _dev(states, torch.int64).reshape(-1, 8)
     n = st.shape[0]
@@ -570,7 +588,7 @@ __all__ = ["states_to_device", "states_to_host", "init_board", "step", "valid_ma
            "augment_examples", "symmetry_flags", "check_policy_columns", "SYMMETRIES", "sample_weights",
            "sample_cdf", "sample_draw", "reanalyse_select", "policies_from_counts", "policies_splice",
            "examples_full_rows", "policies_take", "policy_prune", "fpu_pick", "temperature_schedule",
-           "temperature_pick", "root_temper", "_lib"]
+           "temperature_pick", "root_temper", "score_utility", "_lib"]
 
 
 def greedy_action(states):

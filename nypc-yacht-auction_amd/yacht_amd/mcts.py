@@ -23,8 +23,9 @@ class MCTS:
 
     def _eng(self):
         if self._engine is None:
-            from .replay import fpu_knobs_of
+            from .replay import fpu_knobs_of, score_knobs_of
             fpu = fpu_knobs_of(self.args)  # first-play urgency (args.fpuReduction); unset: off
+            fpu.update(score_knobs_of(self.args))  # the score-margin utility (args.scoreUtility)
             if getattr(self.nnet, "yk_prior", None) == "hash":
                 self._engine = SelfPlayEngine(1, self.args.numMCTSSims, self.args.cpuct, prior="hash", max_moves=1,
                                               **fpu)

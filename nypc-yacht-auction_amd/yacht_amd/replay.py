@@ -200,6 +200,41 @@ def fpu_knobs_of(args) -> dict:
     return dict(fpu_reduction=r, fpu_root_reduction=rr)
 
 
+def check_score_knobs(scoreUtility=None, scoreScale=None):
+    """(weight, scale) of the score-margin utility as (float or None, float or None): both unset is
+    off - (None, None) - else scoreUtility a number in [0, 1] (0 is legal and is not off: it gives the same values
+    as off) and scoreScale a finite number > 0, in game points (a pip is 1000 points).  There is no default
+    scale.  ValueError for anything else, for scoreScale without scoreUtility (alone it would silently do nothing)
+    and for scoreUtility without scoreScale."""
+    def number(name, x, what):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number {what} (unset: off), got {x!r}")
+        return float(x)
+    if scoreUtility is None:
+        if scoreScale is not None:
+            raise ValueError("scoreScale needs scoreUtility: without it the score-margin utility is off and the "
+                             "scale would silently do nothing")
+        return None, None
+    w = number("scoreUtility", scoreUtility, "in [0, 1]")
+    if not 0.0 <= w <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"scoreUtility must lie in [0, 1], got {scoreUtility!r}")
+    if scoreScale is None:
+        raise ValueError("scoreUtility needs scoreScale (game points, > 0): there is no default scale")
+    c = number("scoreScale", scoreScale, "> 0")
+    if not (c > 0.0) or math.isinf(c):
+        raise ValueError(f"scoreScale must be finite and > 0, got {scoreScale!r}")
+    return w, c
+
+
+def score_knobs_of(args) -> dict:
+    """args.scoreUtility / args.scoreScale, checked, as SelfPlayEngine's keyword arguments - what everything that
+    searches for a Coach passes to its engine next to fpu_knobs_of, so the terminal values of every search are in
+    the unit the value head was trained on."""
+    get = args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+    w, c = check_score_knobs(get("scoreUtility", None), get("scoreScale", None))
+    return dict(score_utility=w, score_scale=c)
+
+
 MOVE_TEMPERATURE_RANGE = (0.05, 100.0)  # visit counts are 16-bit: 65535 ** 20 ~ 2e96 is finite in float64
 ROOT_TEMPERATURE_RANGE = (0.25, 10.0)
 
@@ -325,7 +360,8 @@ def sample_segments(examples, gamma: float = 1.0):
 
 def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims: int, n_games: int = -1,
                          maxlen: int = None, stream=None, value_mix: float = 0.0,
-                         value_lambda: float = 1.0, full_only: bool = False) -> ExampleShard:
+                         value_lambda: float = 1.0, full_only: bool = False, score_utility=None,
+                         score_scale=None) -> ExampleShard:
     """Record images (device uint8 [R, nbytes]: every rank's yk_engine_pack_records after the
     all-gather) -> ExampleShard of the first n_games games, keeping the last `maxlen` examples
     (the maxlenOfQueue deque, Coach.py:86-90).  The shard holds only compact arrays (examples and
@@ -339,11 +375,17 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
     full_only (the playout cap): only the examples of full moves are kept.  Every array is first
     built for all moves - the value targets must see whole games - then the rows yk_examples_full_rows names
     are taken, and the last `maxlen` of those kept: maxlen counts training examples.  ``n_searched`` of the
-    shard is the number of moves before the filter."""
+    shard is the number of moves before the filter.
+
+    score_utility (w) and score_scale (c), the score-margin utility (None: off): the shard's
+    ``values`` come from yk_examples_utility_targets - wherever the formulas above read the outcome they read
+    (1 - w) * outcome + w * g, g the squashed final margin of the game's final board in the images - also at
+    (value_mix, value_lambda) = (0, 1), where no root value is needed.  ``outcomes`` and the tuples keep z."""
     beta, lam = check_value_knobs(value_mix, value_lambda)
+    su, sc = check_score_knobs(score_utility, score_scale)
     if full_only:
         every = examples_from_images(images, n_envs, max_moves, sims, n_games=n_games, maxlen=None, stream=stream,
-                                     value_mix=beta, value_lambda=lam)
+                                     value_mix=beta, value_lambda=lam, score_utility=su, score_scale=sc)
         idx = examples_full_rows(images, n_envs, max_moves, sims, n_games=n_games, stream=stream)
         if maxlen is not None:
             idx = idx[max(int(idx.numel()) - max(int(maxlen), 0), 0):].contiguous()
@@ -375,21 +417,29 @@ def examples_from_images(images: torch.Tensor, n_envs: int, max_moves: int, sims
     call("yk_examples_policies", imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, indptr.data_ptr(),
          cols.data_ptr(), vals.data_ptr(), k, v64.data_ptr(), C.byref(nnz), sp)
     pol = dict(pi_indptr=indptr, pi_cols=cols[:k], pi_vals=vals[:k], values64=v64[:n])
-    if (beta, lam) == (0.0, 1.0):
+    if (beta, lam) == (0.0, 1.0) and su is None:
         shard = ExampleShard(states[:n], targets[:n], values[:n], policies=pol)
         shard.n_searched = total
         return shard
     tgt = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
     rootv = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
     missing = C.c_int64()
-    rc = lib().yk_examples_value_targets(imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, beta, lam,
-                                         tgt.data_ptr(), rootv.data_ptr(), C.byref(missing), sp)
+    if su is None:
+        fn = "yk_examples_value_targets"
+        rc = lib().yk_examples_value_targets(imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, beta, lam,
+                                             tgt.data_ptr(), rootv.data_ptr(), C.byref(missing), sp)
+    else:  # the same kernel reading the utility for the outcome
+        fn = "yk_examples_utility_targets"
+        rc = lib().yk_examples_utility_targets(imgs.data_ptr(), R, n_envs, max_moves, sims, n_games, skip, n, beta, lam,
+                                               su, sc, tgt.data_ptr(), rootv.data_ptr(), C.byref(missing), sp)
     if rc == YK_ERR_STATE and missing.value > 0:
         raise ValueError(f"{missing.value} of {n} examples need a root value the record images do not hold: "
                          "value_mix / value_lambda need engines created with record_root_values=True")
     if rc != YK_OK:
-        raise YkError("yk_examples_value_targets", rc)
-    shard = ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n], root_values=rootv[:n])
+        raise YkError(fn, rc)
+    # (at (0, 1) the images need no root values: the shard then carries none)
+    shard = ExampleShard(states[:n], targets[:n], tgt[:n], policies=pol, outcomes=values[:n],
+                         root_values=None if (beta, lam) == (0.0, 1.0) else rootv[:n])
     shard.n_searched = total
     return shard
 
@@ -428,7 +478,7 @@ def check_reanalyse_knobs(reanalyseFraction=0.0, reanalyseSims=None, numMCTSSims
 
 def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: int, cpuct: float, seed: int,
               env_base: int = 0, chunk: int = 4096, env_ids=None, ctr=None, fpu_reduction=None,
-              fpu_root_reduction=None) -> ExampleShard:
+              fpu_root_reduction=None, score_utility=None, score_scale=None) -> ExampleShard:
     """Examples idx of a shard searched again (MuZero's reanalyse): their boards are the roots
     of `sims` simulations of yk_mcts_search on fresh trees with `net` (a YkNet, or a wrapper with yk_net();
     prior="hash": the test prior), and their policy rows and targets become the new search's.
@@ -439,7 +489,8 @@ def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: i
     given.  The last, partial chunk is padded with copies of its first root on the stream ids after the
     call's last one; their searches are dropped (they consume nothing: a stream is a function of its id).
     No root noise is ever added.  fpu_reduction / fpu_root_reduction: the searches run under first-play urgency
-    (SelfPlayEngine's knobs; None: off).
+    (SelfPlayEngine's knobs; None: off).  score_utility / score_scale: their terminal values are the
+    score-margin utility (None: off).
 
     A reanalysed row holds the visit distribution N / sum N of its new search and its target the most visited
     action (the lowest on ties) - also where the stored row was the one-hot of a temp-0 move, so afterwards
@@ -499,7 +550,7 @@ def reanalyse(shard: ExampleShard, idx, *, net=None, prior: str = "net", sims: i
     sp = stream_ptr()
     counts = torch.empty((E, K.ACTION_SIZE), dtype=torch.int32, device="cuda")
     eng = SelfPlayEngine(E, int(sims), float(cpuct), net=net, prior=prior, max_moves=1, fpu_reduction=fpu_reduction,
-                         fpu_root_reduction=fpu_root_reduction)
+                         fpu_root_reduction=fpu_root_reduction, score_utility=score_utility, score_scale=score_scale)
     parts, tparts, n_empty, chunks = [], [], 0, 0
     try:
         for j0 in range(0, m, E):
@@ -636,5 +687,5 @@ def as_device_policies(examples):
 
 
 __all__ = ["ExampleShard", "examples_from_images", "as_device_examples", "as_device_policies", "policies_csr_host",
-           "augment_examples", "check_playout_knobs", "check_forced_knobs", "check_fpu_knobs", "fpu_knobs_of", "policy_prune", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
+           "augment_examples", "check_playout_knobs", "check_forced_knobs", "check_fpu_knobs", "fpu_knobs_of", "check_score_knobs", "score_knobs_of", "policy_prune", "examples_full_rows", "policies_take", "check_sample_knobs", "check_ema_knobs", "sample_rounds", "sample_segments", "check_reanalyse_knobs",
            "reanalyse", "reanalyse_select", "policies_from_counts", "policies_splice"]

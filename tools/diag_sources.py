@@ -118,7 +118,7 @@ ENGINE = [
     (r"^        atomicAdd\(gs \+ 8, \(unsigned long long\)gathered\);\n    \}\n\}\n", "before_last_brace", "    SEL_ACC(3, t_all);\n"),
     (r"^    if \(d\.done\[e\]\) return;\n    // the game's tree and generation, once", "after_line1", XSPAN_BEGIN),
     (r"^    expand_backup_game\(d, e, lane, t, g\);\n", "after", XSPAN_MID),
-    (r"^        select_game<FORCED, FPU>\(d, e, lane, t, g, env_ids, ctr_arr, yk::opt_arg\(ForcedDev\{0\.0, 0\.0\}, fd\.\.\.\), yk::opt_arg\(FpuDev\{0\.0, 0\.0\}, fd\.\.\.\)\);\n    \}\n\}\n\n__device__ __forceinline__ void expand_backup_game",
+    (r"^                                       yk::opt_arg\(UtilDev\{1\.0, 0\.0, 1\.0, nullptr\}, fd\.\.\.\)\);\n    \}\n\}\n\n__device__ __forceinline__ void expand_backup_game",
      "replace_fn", None),
     (r"^        // ---- prior, Ps \* valids \(MCTS.py:88\)", "before", "        SEL_T0(t_x0);\n"),
     (r"^        // numpy pairwise_sum on the leaf:", "before", "        SEL_ACC(8, t_x0);\n        SEL_T0(t_x1);\n"),
